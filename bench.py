@@ -1,9 +1,11 @@
 #!/usr/bin/env python
 """Headline benchmark: molecules/sec of a full QM9 train step (graph_attention_transformer_nonlinear_l2, L_max=2,
-6 blocks, fp32) on N MI355X, data-parallel over molecules, plus the roofline of the dominant kernel and the CPU
-oracle timed on the host cores.
+6 blocks, fp32) on N MI355X, data-parallel over molecules; with --full also the roofline of the dominant kernel, the
+run-to-run spread, the other BASELINE configurations and the CPU oracle timed on the host cores.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5                 # the headline only: set up, warm up, time K steps
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full          # + spread, roofline, sub-records, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +13,11 @@ A step = graph construction from positions + forward + L1 loss + backward + (N>1
 all-reduce) + AdamW update, on a synthetic QM9-shaped batch already resident in HBM (128 molecules x 18 atoms per
 GPU, ~200 directed edges per molecule at r = 5 A).  Weak scaling: per-GPU batch fixed.
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR writes what the last timed step computed (loss, predictions, the gradient it applied and the
+parameters after its update) as DIR/<name>.npy.  The inputs are seeded, and the last timed step starts from the seeded
+training state after setup (optimizer buffers, step counts, host generator), so two runs with the same arguments (two
+builds) give it the same inputs and compare output for output.
 """
 import argparse
 import json
@@ -34,25 +41,32 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the run-to-run spread (--repeats), the roofline and "
+                         "per-kernel figures of the dominant kernels, the sub-records of the other BASELINE configurations and "
+                         "the CPU-oracle baseline.  Without it the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at "
+                         "most 64 MB in all: larger arrays are a fixed, seeded sample)")
     ap.add_argument("--batch", type=int, default=128, help="molecules per GPU (reference script: 128)")
     ap.add_argument("--atoms", type=int, default=18)
     ap.add_argument("--side", type=float, default=6.5, help="cube edge of the synthetic molecules (6.5 -> ~200 edges)")
     ap.add_argument("--dominant", default="",
-                    help="kernel-name substring timed with HIP events for the roofline line (default: the dominant SeparableFCTP kernel, picked by one untimed step after the warm-up)")
+                    help="--full: kernel-name substring timed with HIP events for the roofline line (default: the dominant SeparableFCTP kernel, picked by one untimed step after the warm-up)")
     ap.add_argument("--cpu-molecules", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--no-cpu-full-batch", dest="cpu_full_batch", action="store_false",
-                    help="skip the like-for-like CPU run at the bench batch (3 steps of ~15 s)")
+                    help="--full: skip the like-for-like CPU run at the bench batch (3 steps of ~15 s)")
     ap.add_argument("--cpu-threads", type=int, default=8,
-                    help="threads of the CPU-oracle leg (BASELINE.md section 2: torch.set_num_threads(8)); capped by the host's cores")
+                    help="--full: threads of the CPU-oracle leg (BASELINE.md section 2: torch.set_num_threads(8)); capped by the host's cores")
     ap.add_argument("--cpu-baseline-only", action="store_true",
-                    help="internal: run only the CPU-oracle leg and print its JSON object (the default run starts this as a "
+                    help="internal: run only the CPU-oracle leg and print its JSON object (a --full run starts this as a "
                          "background process beside the GPU sub-records)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-oracle baseline")
     ap.add_argument("--repeats", type=int, default=3,
-                    help="timed regions of K steps each: 1 = only the contract's region; 3 (default) adds two repeats for the spread")
+                    help="--full: timed regions of K steps each: 1 = only the contract's region; 3 (default) adds two repeats for the spread")
     ap.add_argument("--no-sub-records", dest="sub_records", action="store_false",
-                    help="skip the compact records of the other BASELINE configurations (bf16 mode, MD17 L2 / L3, OC20)")
+                    help="--full: skip the compact records of the other BASELINE configurations (bf16 mode, MD17 L2 / L3, OC20)")
     ap.add_argument("--overlap-wgrad", action="store_true",
                     help="A/B switch: weight gradients of the fused SeparableFCTP on a side stream beside the data gradient")
     ap.add_argument("--workload", default="qm9", choices=["qm9", "md17_l2", "md17_l3", "oc20"],
@@ -173,6 +187,7 @@ def build_workload(args, dev, rank, world):
     from equiformer_amd.synthetic import md17_aspirin_batch, qm9_like_batch
     W = WORKLOADS[args.workload]
     torch.manual_seed(0)
+    outs = {}  # the predictions of the latest step (detached; inside a captured step: the tensors every replay rewrites)
     if args.workload == "qm9":
         model = nets.model_entrypoint(W["model"])(irreps_in="5x0e", radius=5.0, num_basis=128).to(dev).train()
         d = {k: v.to(dev) for k, v in qm9_like_batch(args.batch, args.atoms, side=args.side, seed=1000 + rank).items()}
@@ -182,6 +197,7 @@ def build_workload(args, dev, rank, world):
 
         def fwd_loss(graph=None):
             pred = model(f_in=None, pos=d["pos"], batch=d["batch"], node_atom=d["z"], graph=graph or static_graph)
+            outs["energy"] = pred.detach()
             return (pred.squeeze() - d["y"]).abs().mean()  # L1Loss (main_qm9.py:188-189)
 
         def build_graph(into):  # the radius graph of the step's batch, rebuilt EVERY step (outside the captured part)
@@ -200,6 +216,7 @@ def build_workload(args, dev, rank, world):
 
         def fwd_loss(graph=None):  # L2MAE force loss + L1 energy loss with the scripts' weights (se_l2 / se_l3 target@aspirin.sh)
             E, F = model(node_atom=d["z"], pos=d["pos"], batch=d["batch"], graph=graph)
+            outs["energy"], outs["forces"] = E.detach(), F.detach()
             return (E - ty).abs().mean() + W["wf"] * (F - tf).norm(dim=1).mean()
 
         def build_graph(into):
@@ -218,7 +235,9 @@ def build_workload(args, dev, rank, world):
         y = y.to(dev)
 
         def fwd_loss():
-            return (model(data).squeeze() - y).abs().mean()
+            pred = model(data)
+            outs["energy"] = pred.detach()
+            return (pred.squeeze() - y).abs().mean()
         g, _, _ = EdgeGraph.from_radius_pbc(data.pos, data.cell, data.batch, 5.0, 500)
         units = B
         text = ("OC20 IS2RE %s train step (periodic radius graph on the device + fwd + L1 + bwd + AdamW), %d structures/GPU x "
@@ -249,7 +268,8 @@ def build_workload(args, dev, rank, world):
         return captured.step(build_graph)
     reducer.timing = world > 1
     return dict(step=step_graph if captured is not None else step_eager, step_eager=step_eager, units=units, nodes=g.N,
-                edges=g.E, text=text, model_name=W["model"], captured=captured, reducer=reducer)
+                edges=g.E, text=text, model_name=W["model"], captured=captured, reducer=reducer,
+                opt=opt, outputs=outs)
 
 
 def cpu_baseline_other(args):
@@ -392,10 +412,58 @@ def roofline_of(prof, dt_s, mode, with_pmc=True):
     return out
 
 
-def measure(args, dev, rank, world, workload, mode, steps, warmup, regions=("sfcx",)):
+def _train_state(opt):
+    """What a train step advances: the optimizer's flat buffers and step counts, and the host generator the dropout seeds are
+    drawn from (parameters alias flat_p).  Not the skip marks of gradient-less parameters in flat_wd: they are set by the
+    first step and stay (a replayed graph does not rewrite them)."""
+    bufs = [opt.flat_p, opt.flat_m, opt.flat_v] + ([opt.flat_ema] if opt.flat_ema is not None else [])
+    return dict(bufs=[(b, b.clone()) for b in bufs], step=opt._step, lag=list(opt._lag), rng=torch.get_rng_state())
+
+
+def _restore_train_state(opt, st):
+    """Back to `st`, IN PLACE: a captured step keeps the addresses of the buffers it read and wrote."""
+    with torch.no_grad():
+        for b, saved in st["bufs"]:
+            b.copy_(saved)
+    opt._step, opt._lag = st["step"], list(st["lag"])
+    for i, p in enumerate(opt._params):
+        opt.state[p]["step"] = opt._step - opt._lag[i]
+    torch.set_rng_state(st["rng"])
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(wl, loss, outdir):
+    """What the last timed step computed, as the caller of the step holds it afterwards: loss, predictions, the (reduced)
+    gradient the optimizer applied and the parameters after the update -> outdir/<name>.npy.  Arrays that would take the
+    dump over DUMP_BYTES are replaced by a fixed sample (seeded, sorted indices: `<name>_index.npy`)."""
+    import numpy as np
+    opt = wl["opt"]
+    arrs = {"loss": np.array([loss], dtype=np.float64)}
+    for k, v in wl["outputs"].items():
+        arrs[k] = v.float().cpu().numpy()
+    arrs["grads"] = torch.cat([v.reshape(-1) for v in opt._gviews]).cpu().numpy()
+    arrs["params"] = torch.cat([p.detach().reshape(-1) for p in opt._params]).cpu().numpy()
+    small = sum(a.nbytes for k, a in arrs.items() if k not in ("grads", "params"))
+    per_big = (DUMP_BYTES - small) // 2
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrs.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > per_big:  # (float32: an index costs 8 bytes per kept element in float64, a value 4)
+            n = per_big // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            np.save(os.path.join(outdir, k + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, k + ".npy"), a)
+    return sorted(arrs)
+
+
+def measure(args, dev, rank, world, workload, mode, steps, warmup, regions=("sfcx",), dump=""):
     """Build `workload`, run `warmup` untimed steps, then one timed region of EXACTLY `steps` steps per entry of `regions`
     (barrier + synchronize on both sides, max over ranks).  An entry is the HIP-event filter of that region: a kernel-name
-    substring, "" for every matrix-core kernel, None for no events.  -> (workload dict, [(seconds, event records)], final loss)"""
+    substring, "" for every matrix-core kernel, None for no events.  dump: directory for what the last step of the FIRST
+    region computed (rank 0).  -> (workload dict, [(seconds, event records)], final loss)"""
     from equiformer_amd import lib, ops
     prev = ops.set_matrix_mode(mode)
     a2 = argparse.Namespace(**vars(args))
@@ -408,6 +476,12 @@ def measure(args, dev, rank, world, workload, mode, steps, warmup, regions=("sfc
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    # the seeded state after setup.  The pre-warm is a time-bounded number of steps: what they advance is put back afterwards
+    # (a captured graph made there stays: it addresses the same buffers).  The LAST timed step starts from this state again:
+    # the weight gradients are summed with float atomics, whose order changes from run to run, and AdamW's normalisation
+    # turns that rounding in near-zero gradient elements into parameter differences that grow with every step; restored,
+    # the last step has the same inputs in every run and what it computes differs by one step's rounding at most
+    state0 = _train_state(wl["opt"])
     prewarm = float(getattr(args, "prewarm_s", 0.0) or 0.0)
     if prewarm > 0:
         t_end = time.perf_counter() + prewarm
@@ -421,9 +495,11 @@ def measure(args, dev, rank, world, workload, mode, steps, warmup, regions=("sfc
                 go = flag.item() > 0.0
             if not go:
                 break
+        torch.cuda.synchronize()
+        _restore_train_state(wl["opt"], state0)
     for _ in range(warmup):
         step()
-    regions = [r for r in regions if r != "graph" or wl["captured"] is not None]
+    regions = [r for r in regions if r != "graph" or wl["captured"] is not None] or [None]
     step_eager = wl["step_eager"]
     if "auto" in regions:
         # one more untimed step with events on the SeparableFCTP kernels picks the dominant one; the timed region then carries
@@ -445,7 +521,9 @@ def measure(args, dev, rank, world, workload, mode, steps, warmup, regions=("sfc
         ops.deferred_weight_gradient_stats(reset=True)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            if i == steps - 1:  # (copies queued behind the previous step: they overlap its tail on the host side)
+                _restore_train_state(wl["opt"], state0)
             loss = run()
         barrier()
         dt = time.perf_counter() - t0
@@ -465,6 +543,8 @@ def measure(args, dev, rank, world, workload, mode, steps, warmup, regions=("sfc
                               "n_ranks_seen": torch.distributed.get_world_size()}
         out.append((t.item(), prof, flt))
         wl["deferred_weight_gradients"] = dict(ops.deferred_weight_gradient_stats(), steps=steps)
+        if dump and rank == 0 and len(out) == 1:
+            wl["dumped"] = dump_outputs(wl, float(loss.item()), dump)
     loss = float(loss.item())
     ops.set_matrix_mode(prev)
     return wl, out, loss
@@ -559,10 +639,15 @@ def main():
     # figures of `roofline` then come from region 2, the same K steps launched eagerly with events on the dominant kernel (a
     # replayed launch cannot carry host-side events; a kernel's duration does not depend on how it was launched, and the
     # rocprofv3 kernel trace of this command, profiles/r06, sees the replayed launches).
-    first = args.dominant if args.dominant else "auto"
-    regions = (first, "", None) if args.repeats >= 3 else ((first, "") if args.repeats == 2 else (first,))
+    # Without --full only that region runs: the HIP-graph replay where the step is captured, else eager launches without events.
+    if args.full:
+        first = args.dominant if args.dominant else "auto"
+        regions = (first, "", None) if args.repeats >= 3 else ((first, "") if args.repeats == 2 else (first,))
+    else:
+        regions = ()
     regions = ("graph",) + regions  # (dropped by measure() where the step is not captured)
-    wl, regs, loss = measure(args, dev, rank, world, args.workload, args.matrix_mode, args.steps, args.warmup, regions)
+    wl, regs, loss = measure(args, dev, rank, world, args.workload, args.matrix_mode, args.steps, args.warmup, regions,
+                             dump=args.dump_outputs)
     graphed = regs[0][2] == "graph"
     dt = regs[0][0]
     irf = 1 if (graphed and len(regs) > 1) else 0  # the region whose events feed `roofline`
@@ -601,108 +686,111 @@ def main():
             out["n_ranks_seen"] = pr["n_ranks_seen"]
             out["allreduce_ms"] = max(pr["allreduce_ms"])  # per step: head collective + exposed wait on the tail, slowest rank
             out["config"]["per_rank"] = pr
-        vals = [wl["units"] * world * args.steps / d for d, _, _ in regs]
-        what = {"graph": "the step replayed as one HIP graph", "": "eager launches, events on every matrix-core launch",
-                None: "eager launches, no events"}
-        out["spread"] = {"values": vals, "min": min(vals), "max": max(vals),
-                         "regions": [what.get(f, "eager launches, HIP events on the launches of `%s`" % f) for _, _, f in regs],
-                         "note": "the same %d steps timed %d times back to back in this process; [0] = `value`" % (args.steps, len(vals))}
         out["config"]["hip_graph"] = bool(graphed)
         if graphed and wl.get("captured") is not None:
             out["config"]["hip_graph_replays"] = wl["captured"].replays
             out["config"]["hip_graph_eager_steps"] = wl["captured"].eager_steps
-        rf = roofline_of(prof, dt_rf, args.matrix_mode)
-        if rf is not None and graphed:
-            rf["measured_in"] = ("region [%d] of `spread`: the same %d steps launched eagerly with HIP events on this kernel's launches "
-                                 "(%.3f ms/step there); `value` is region [0], where the step is one graph launch" % (irf, args.steps, 1e3 * dt_rf / args.steps))
-        allprof = regs[irf + 1][1] if len(regs) > irf + 1 else prof
-        if rf is not None:
-            out["roofline"] = rf
-            # the other matrix-core kernels of the step, same accounting (second region; not part of the contract)
-            others = []
-            for n2, r2 in sorted(allprof.items(), key=lambda kv: -kv[1]["total_ms"]):
-                if n2 == rf["kernel"] or r2["flops"] <= 0:
-                    continue
-                pk, _ = kernel_peak(n2, args.matrix_mode)
-                tf = r2["flops"] / r2["total_ms"] / 1e9
-                others.append({"kernel": n2, "launches": r2["launches"], "avg_launch_ms": r2["total_ms"] / r2["launches"],
-                               "achieved": tf, "peak": pk, "frac": tf / pk,
-                               "share_of_step": r2["total_ms"] / (1e3 * regs[irf + 1][0] if len(regs) > irf + 1 else 1e3 * dt_rf)})
-            out["roofline"]["others"] = others[:8]
-        # the two kernels BASELINE.json's north_star asks to be stated against the gfx950 peaks (not part of the contract
-        # line): HBM GB/s of the per-destination softmax + scatter (algorithmic bytes 1 940 E + 1 920 N per call,
-        # SURVEY 8d) and MFMA rate of the radial MLP's widest layer (E x 64 -> 960)
-        extra = {}
-        sc = allprof.get("attn_fwd")
-        if sc:
-            byts = 1940.0 * n_edges + 1920.0 * n_nodes
-            gbps = byts * sc["launches"] / sc["total_ms"] / 1e6
-            extra["scatter"] = {"kernel": "attn_fwd (segment softmax + aggregation)", "bound": "hbm", "achieved": gbps,
-                                "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": gbps / PEAK_HBM_GBPS,
-                                "avg_launch_ms": sc["total_ms"] / sc["launches"], "algorithmic_bytes_per_launch": byts}
-            pmc, note = _pmc_record()
-            if pmc is not None and "attn_fwd" in pmc:  # rocprofv3 FETCH_SIZE / WRITE_SIZE of this build (tools/gpu_profile.sh)
-                tb = pmc["attn_fwd"]["hbm_bytes_per_launch"]
-                extra["scatter"].update({"traffic": tb, "traffic_over_algorithmic": tb / byts,
-                                         "counter_gbps": tb * sc["launches"] / sc["total_ms"] / 1e6,
-                                         "counter_frac": tb * sc["launches"] / sc["total_ms"] / 1e6 / PEAK_HBM_GBPS,
-                                         "traffic_source": note})
-        # the widest E-row GEMM with a memory A operand and an [N, K] weight = the radial MLP's last layer
-        rad = [(n2, r2) for n2, r2 in allprof.items()
-               if (n2.startswith("gemm_rows_") and n2.endswith("_mem_nk")) or n2 in ("gemmx_group_nk_edge", "gemm_group_nk")]
-        if rad:
-            n2, r2 = max(rad, key=lambda kv: kv[1]["flops"] / kv[1]["launches"])
-            tf = r2["flops"] / r2["total_ms"] / 1e9
-            pk, _ = kernel_peak(n2, args.matrix_mode)
-            extra["radial_mlp"] = {"kernel": n2 + " (edge-row nn.Linear launches of the radial bank: 128 -> G x 64, G x (64 -> 64), "
-                                             "G x (64 -> 960); the last is 94 % of their flops)", "bound": "mfma", "achieved": tf,
-                                   "peak": pk, "unit": "TFLOP/s", "frac": tf / pk, "frac_of_fp32_peak": tf / PEAK_F32_MFMA_TFLOPS,
-                                   "avg_launch_ms": r2["total_ms"] / r2["launches"]}
-            pmc, note = _pmc_record()
-            if pmc is not None and "gemmx_rows_wide" in pmc:
-                # the last layer's own kernel (E x 64 -> 7 x 960): SQ_INSTS_MFMA per launch over its kernel-trace duration
-                w = pmc["gemmx_rows_wide"]
-                extra["radial_mlp"]["widest_layer_kernel"] = {
-                    "kernel": "gemmx_rows_wide_kernel", "mfma_insts_per_launch": w.get("mfma_insts_per_launch"),
-                    "avg_us_kernel_trace": w.get("avg_us_kernel_trace"), "mfma_busy": w.get("mfma_busy"),
-                    "hbm_bytes_per_launch": w.get("hbm_bytes_per_launch"), "traffic_source": note}
-        # whole step against the HBM roofline of SURVEY 8d: 3.0 MB algorithmic bytes per molecule-step at E = 200
-        if args.workload == "qm9":
-            b_alg = 6 * (172800.0 + 1112.0 * n_edges / args.batch) + 0.29e6 + 0.33e6
-            extra["step_hbm_roofline"] = {"algorithmic_bytes_per_molecule": b_alg,
-                                          "molecules_per_s_at_peak": PEAK_HBM_GBPS * 1e9 / b_alg * world,
-                                          "frac": out["value"] / (PEAK_HBM_GBPS * 1e9 / b_alg * world)}
-        out["north_star_kernels"] = extra
+        if wl.get("dumped"):
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": wl["dumped"]}
         print("[bench] gpu part done: %.1f %s, %.2f ms/step" % (out["value"], out["unit"], out["ms_per_step"]),
               file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline and args.workload == "qm9":
-            # the CPU-oracle leg as a background process (its own interpreter, --cpu-threads threads): it runs beside the GPU
-            # sub-records below, the headline figures above are already measured
-            import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--batch", str(args.batch), "--atoms", str(args.atoms),
-                   "--side", str(args.side), "--cpu-molecules", str(args.cpu_molecules), "--cpu-steps", str(args.cpu_steps),
-                   "--cpu-threads", str(args.cpu_threads)] + ([] if args.cpu_full_batch else ["--no-cpu-full-batch"])
-            cpu_proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
-        # the other BASELINE configurations, measured in this same run (one GPU; the headline workload only)
-        if world == 1 and args.sub_records and args.workload == "qm9" and args.matrix_mode == "split":
-            del wl, regs
-            torch.cuda.empty_cache()
-            subs = []
-            # (qm9 / fp32: exact-fp32 MFMA in every matrix step -- the like-for-like figure against the reference's --no-amp)
-            for wname, mode in (("qm9", "bf16"), ("qm9", "fp32"), ("oc20", "split"), ("md17_l2", "split"), ("md17_l3", "split")):
-                subs.append(sub_record(args, dev, wname, mode))
-                print("[bench] sub-record %s/%s: %s" % (wname, mode, {k: subs[-1].get(k) for k in ("value", "ms_per_step", "error")}),
-                      file=sys.stderr, flush=True)
-            out["configs"] = subs
-        if cpu_proc is not None:
-            try:
-                txt, _ = cpu_proc.communicate(timeout=600)
-                out["cpu_baseline"] = json.loads([ln for ln in txt.splitlines() if ln.startswith("{")][-1])
-            except Exception as exc:  # the leg must not take the GPU line down
-                cpu_proc.kill()
-                out["cpu_baseline"] = {"error": repr(exc)[:200]}
-        elif world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_other(args)
+        if args.full:
+            vals = [wl["units"] * world * args.steps / d for d, _, _ in regs]
+            what = {"graph": "the step replayed as one HIP graph", "": "eager launches, events on every matrix-core launch",
+                    None: "eager launches, no events"}
+            out["spread"] = {"values": vals, "min": min(vals), "max": max(vals),
+                             "regions": [what.get(f, "eager launches, HIP events on the launches of `%s`" % f) for _, _, f in regs],
+                             "note": "the same %d steps timed %d times back to back in this process; [0] = `value`" % (args.steps, len(vals))}
+            rf = roofline_of(prof, dt_rf, args.matrix_mode)
+            if rf is not None and graphed:
+                rf["measured_in"] = ("region [%d] of `spread`: the same %d steps launched eagerly with HIP events on this kernel's launches "
+                                     "(%.3f ms/step there); `value` is region [0], where the step is one graph launch" % (irf, args.steps, 1e3 * dt_rf / args.steps))
+            allprof = regs[irf + 1][1] if len(regs) > irf + 1 else prof
+            if rf is not None:
+                out["roofline"] = rf
+                # the other matrix-core kernels of the step, same accounting (second region; not part of the contract)
+                others = []
+                for n2, r2 in sorted(allprof.items(), key=lambda kv: -kv[1]["total_ms"]):
+                    if n2 == rf["kernel"] or r2["flops"] <= 0:
+                        continue
+                    pk, _ = kernel_peak(n2, args.matrix_mode)
+                    tf = r2["flops"] / r2["total_ms"] / 1e9
+                    others.append({"kernel": n2, "launches": r2["launches"], "avg_launch_ms": r2["total_ms"] / r2["launches"],
+                                   "achieved": tf, "peak": pk, "frac": tf / pk,
+                                   "share_of_step": r2["total_ms"] / (1e3 * regs[irf + 1][0] if len(regs) > irf + 1 else 1e3 * dt_rf)})
+                out["roofline"]["others"] = others[:8]
+            # the two kernels BASELINE.json's north_star asks to be stated against the gfx950 peaks (not part of the contract
+            # line): HBM GB/s of the per-destination softmax + scatter (algorithmic bytes 1 940 E + 1 920 N per call,
+            # SURVEY 8d) and MFMA rate of the radial MLP's widest layer (E x 64 -> 960)
+            extra = {}
+            sc = allprof.get("attn_fwd")
+            if sc:
+                byts = 1940.0 * n_edges + 1920.0 * n_nodes
+                gbps = byts * sc["launches"] / sc["total_ms"] / 1e6
+                extra["scatter"] = {"kernel": "attn_fwd (segment softmax + aggregation)", "bound": "hbm", "achieved": gbps,
+                                    "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": gbps / PEAK_HBM_GBPS,
+                                    "avg_launch_ms": sc["total_ms"] / sc["launches"], "algorithmic_bytes_per_launch": byts}
+                pmc, note = _pmc_record()
+                if pmc is not None and "attn_fwd" in pmc:  # rocprofv3 FETCH_SIZE / WRITE_SIZE of this build (tools/gpu_profile.sh)
+                    tb = pmc["attn_fwd"]["hbm_bytes_per_launch"]
+                    extra["scatter"].update({"traffic": tb, "traffic_over_algorithmic": tb / byts,
+                                             "counter_gbps": tb * sc["launches"] / sc["total_ms"] / 1e6,
+                                             "counter_frac": tb * sc["launches"] / sc["total_ms"] / 1e6 / PEAK_HBM_GBPS,
+                                             "traffic_source": note})
+            # the widest E-row GEMM with a memory A operand and an [N, K] weight = the radial MLP's last layer
+            rad = [(n2, r2) for n2, r2 in allprof.items()
+                   if (n2.startswith("gemm_rows_") and n2.endswith("_mem_nk")) or n2 in ("gemmx_group_nk_edge", "gemm_group_nk")]
+            if rad:
+                n2, r2 = max(rad, key=lambda kv: kv[1]["flops"] / kv[1]["launches"])
+                tf = r2["flops"] / r2["total_ms"] / 1e9
+                pk, _ = kernel_peak(n2, args.matrix_mode)
+                extra["radial_mlp"] = {"kernel": n2 + " (edge-row nn.Linear launches of the radial bank: 128 -> G x 64, G x (64 -> 64), "
+                                                 "G x (64 -> 960); the last is 94 % of their flops)", "bound": "mfma", "achieved": tf,
+                                       "peak": pk, "unit": "TFLOP/s", "frac": tf / pk, "frac_of_fp32_peak": tf / PEAK_F32_MFMA_TFLOPS,
+                                       "avg_launch_ms": r2["total_ms"] / r2["launches"]}
+                pmc, note = _pmc_record()
+                if pmc is not None and "gemmx_rows_wide" in pmc:
+                    # the last layer's own kernel (E x 64 -> 7 x 960): SQ_INSTS_MFMA per launch over its kernel-trace duration
+                    w = pmc["gemmx_rows_wide"]
+                    extra["radial_mlp"]["widest_layer_kernel"] = {
+                        "kernel": "gemmx_rows_wide_kernel", "mfma_insts_per_launch": w.get("mfma_insts_per_launch"),
+                        "avg_us_kernel_trace": w.get("avg_us_kernel_trace"), "mfma_busy": w.get("mfma_busy"),
+                        "hbm_bytes_per_launch": w.get("hbm_bytes_per_launch"), "traffic_source": note}
+            # whole step against the HBM roofline of SURVEY 8d: 3.0 MB algorithmic bytes per molecule-step at E = 200
+            if args.workload == "qm9":
+                b_alg = 6 * (172800.0 + 1112.0 * n_edges / args.batch) + 0.29e6 + 0.33e6
+                extra["step_hbm_roofline"] = {"algorithmic_bytes_per_molecule": b_alg,
+                                              "molecules_per_s_at_peak": PEAK_HBM_GBPS * 1e9 / b_alg * world,
+                                              "frac": out["value"] / (PEAK_HBM_GBPS * 1e9 / b_alg * world)}
+            out["north_star_kernels"] = extra
+            if world == 1 and not args.no_cpu_baseline and args.workload == "qm9":
+                # the CPU-oracle leg as a background process (its own interpreter, --cpu-threads threads): it runs beside the GPU
+                # sub-records below, the headline figures above are already measured
+                import subprocess
+                cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--batch", str(args.batch), "--atoms", str(args.atoms),
+                       "--side", str(args.side), "--cpu-molecules", str(args.cpu_molecules), "--cpu-steps", str(args.cpu_steps),
+                       "--cpu-threads", str(args.cpu_threads)] + ([] if args.cpu_full_batch else ["--no-cpu-full-batch"])
+                cpu_proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+            # the other BASELINE configurations, measured in this same run (one GPU; the headline workload only)
+            if world == 1 and args.sub_records and args.workload == "qm9" and args.matrix_mode == "split":
+                del wl, regs
+                torch.cuda.empty_cache()
+                subs = []
+                # (qm9 / fp32: exact-fp32 MFMA in every matrix step -- the like-for-like figure against the reference's --no-amp)
+                for wname, mode in (("qm9", "bf16"), ("qm9", "fp32"), ("oc20", "split"), ("md17_l2", "split"), ("md17_l3", "split")):
+                    subs.append(sub_record(args, dev, wname, mode))
+                    print("[bench] sub-record %s/%s: %s" % (wname, mode, {k: subs[-1].get(k) for k in ("value", "ms_per_step", "error")}),
+                          file=sys.stderr, flush=True)
+                out["configs"] = subs
+            if cpu_proc is not None:
+                try:
+                    txt, _ = cpu_proc.communicate(timeout=600)
+                    out["cpu_baseline"] = json.loads([ln for ln in txt.splitlines() if ln.startswith("{")][-1])
+                except Exception as exc:  # the leg must not take the GPU line down
+                    cpu_proc.kill()
+                    out["cpu_baseline"] = {"error": repr(exc)[:200]}
+            elif world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_other(args)
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

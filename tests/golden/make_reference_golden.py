@@ -109,25 +109,33 @@ def _oc20_data(ins, cell=7.0):
                            natoms=torch.bincount(batch, minlength=B))
 
 
-def reference_outputs(reference="/root/reference", shims=None, log=print):
+def reference_outputs(reference="/root/reference", shims=None, log=print, with_reference=True):
     """{fixture tag: {output name: array}} computed by the reference's own model classes, and the same from the oracle
-    restatement (oracle/nets.py) with identical weights: -> (ref_outs, oracle_outs)."""
-    import_reference(reference, shims)
-    from nets.graph_attention_transformer import GraphAttentionTransformer as RefQM9  # [ref: :737-899]
-    from nets.graph_attention_transformer_md17 import GraphAttentionTransformerMD17 as RefMD17  # [ref: :127-327]
-    from nets.graph_attention_transformer_oc20 import GraphAttentionTransformerOC20 as RefOC20  # [ref: :85-381]
-    from nets.dp_attention_transformer import DotProductAttentionTransformer as RefDP  # [ref: :255-411]
-    from nets.dp_attention_transformer_md17 import DotProductAttentionTransformerMD17 as RefDPMD17  # [ref: :57-235]
-    from nets.equiformer_md17_dens import Equiformer_MD17_DeNS as RefDeNS  # [ref: :55-354]
+    restatement (oracle/nets.py) with identical weights: -> (ref_outs, oracle_outs).  with_reference=False: the oracle's
+    outputs only (ref_outs empty; no reference checkout needed)."""
+    RefQM9 = RefMD17 = RefOC20 = RefDP = RefDPMD17 = RefDeNS = None
+    if with_reference:
+        import_reference(reference, shims)
+        from nets.graph_attention_transformer import GraphAttentionTransformer as RefQM9  # [ref: :737-899]
+        from nets.graph_attention_transformer_md17 import GraphAttentionTransformerMD17 as RefMD17  # [ref: :127-327]
+        from nets.graph_attention_transformer_oc20 import GraphAttentionTransformerOC20 as RefOC20  # [ref: :85-381]
+        from nets.dp_attention_transformer import DotProductAttentionTransformer as RefDP  # [ref: :255-411]
+        from nets.dp_attention_transformer_md17 import DotProductAttentionTransformerMD17 as RefDPMD17  # [ref: :57-235]
+        from nets.equiformer_md17_dens import Equiformer_MD17_DeNS as RefDeNS  # [ref: :55-354]
     from oracle import nets as onets
     R, O = {}, {}
     t = torch.as_tensor
 
     def pair(ocls, rcls, seed, okw, rargs=(), rkw=None):
         om = fill_deterministic(ocls(**okw).eval(), seed).double()  # weights rounded to fp32 like make_golden.py
+        if rcls is None:
+            return om, None
         rm = as_double(rcls(*rargs, **(okw if rkw is None else rkw)))
         copy_by_name(om, rm)
         return om, rm
+
+    def runs(rm, om):
+        return [(m, store) for m, store in ((rm, R), (om, O)) if m is not None]
 
     # ---- QM9-shaped, non-linear and linear messages [ref: GraphAttentionTransformer.forward :864-899]
     for tag, seed, kw, gkeys in (
@@ -136,7 +144,7 @@ def reference_outputs(reference="/root/reference", shims=None, log=print):
         ins, _ = load_fixture(tag)
         om, rm = pair(onets.GraphAttentionTransformer, RefQM9, seed,
                       dict(irreps_in="5x0e", max_radius=5.0, number_of_basis=32, **kw))
-        for m, store in ((rm, R), (om, O)):
+        for m, store in runs(rm, om):
             e = m(f_in=None, pos=t(ins["pos"]).double(), batch=t(ins["batch"]), node_atom=t(ins["z"]))
             loss = (e.squeeze() - t(ins["y"]).double()).abs().mean()
             if tag == "qm9_small":
@@ -154,7 +162,7 @@ def reference_outputs(reference="/root/reference", shims=None, log=print):
             ("dp_md17_small", onets.DotProductAttentionTransformerMD17, RefDPMD17, 19, mg.SMALL_DP_L2)):
         ins, _ = load_fixture(tag)
         om, rm = pair(ocls, rcls, seed, dict(irreps_in="64x0e", max_radius=5.0, number_of_basis=32, basis_type="exp", **kw))
-        for m, store in ((rm, R), (om, O)):
+        for m, store in runs(rm, om):
             e, f = m(node_atom=t(ins["z"]), pos=t(ins["pos"]).double(), batch=t(ins["batch"]))
             store[tag] = dict(energy=e.detach().numpy(), forces=f.detach().numpy())
 
@@ -164,7 +172,7 @@ def reference_outputs(reference="/root/reference", shims=None, log=print):
             ("e3_qm9_small", onets.GraphAttentionTransformer, RefQM9, 16, mg.SMALL_E3_L2)):
         ins, _ = load_fixture(tag)
         om, rm = pair(ocls, rcls, seed, dict(irreps_in="5x0e", max_radius=5.0, number_of_basis=32, **kw))
-        for m, store in ((rm, R), (om, O)):
+        for m, store in runs(rm, om):
             e = m(f_in=None, pos=t(ins["pos"]).double(), batch=t(ins["batch"]), node_atom=t(ins["z"]))
             store[tag] = dict(energy=e.detach().numpy())
 
@@ -175,17 +183,17 @@ def reference_outputs(reference="/root/reference", shims=None, log=print):
         ins, _ = load_fixture(tag)
         om, rm = pair(onets.GraphAttentionTransformerOC20, RefOC20, seed, kw, rargs=(None, None, 1),
                       rkw=dict(kw, use_pbc=True, otf_graph=False))
-        ro = rm(_oc20_data(ins))
+        ro = rm(_oc20_data(ins)) if rm is not None else None
         oo = om(t(ins["z"]), t(ins["tags"]), t(ins["pos"]).double(), t(ins["batch"]), edge_index=t(ins["edge_index"]),
                 offsets=t(ins["offsets"]).double())
-        for out, store in ((ro, R), (oo, O)):
+        for out, store in [(x, st) for x, st in ((ro, R), (oo, O)) if x is not None]:
             out = out if isinstance(out, tuple) else (out,)
             store[tag] = dict(zip(("energy", "aux"), (x.detach().numpy() for x in out)))
 
     # ---- DeNS [ref: Equiformer_MD17_DeNS.forward :238-354]
     ins, _ = load_fixture("dens_small")
     om, rm = pair(onets.Equiformer_MD17_DeNS, RefDeNS, 18, dict(mg.SMALL_DENS))
-    for m, store in ((rm, R), (om, O)):
+    for m, store in runs(rm, om):
         data = SimpleNamespace(z=t(ins["z"]), pos=t(ins["pos"]).double(), batch=t(ins["batch"]),
                                force=t(ins["force"]).double(), noise_mask=t(ins["noise_mask"]))
         e, dy = m(data)
@@ -207,7 +215,145 @@ def check_all(reference="/root/reference", shims=None, write=False, log=print):
             arrs = {"in::" + k: v for k, v in ins.items()}
             arrs.update({"out::" + k: np.asarray(v) for k, v in got.items()})
             np.savez_compressed(os.path.join(HERE, tag + ".npz"), **arrs)
-    missing = sorted(f[:-4] for f in os.listdir(HERE) if f.endswith(".npz") and f[:-4] not in R)
+    missing = sorted(f[:-4] for f in os.listdir(HERE) if f.endswith(".npz") and f[:-4] not in R and f != os.path.basename(PIN))
+    assert not missing, "fixtures without a reference run: %s" % missing
+    return errs
+
+
+# ---- reference_pin.npz: what tests/test_reference_pin.py checks the oracle and the product against, recorded from the
+# reference's own model code by `--pin` (the tests run without a reference checkout)
+PIN = os.path.join(HERE, "reference_pin.npz")
+FULL_SIZE = (("graph_attention_transformer_nonlinear_l2", 3_531_715),
+             ("graph_attention_transformer_nonlinear_exp_l2_md17", 3_496_001),
+             ("graph_attention_transformer_nonlinear_exp_l3_md17", 5_500_865))
+OTF_CFG = dict(irreps_node_embedding="256x0e+128x1e", num_layers=2, irreps_sh="1x0e+1x1e", max_radius=5.0, number_of_basis=128,
+               fc_neurons=[64, 64], irreps_feature="512x0e", irreps_head="32x0e+16x1e", num_heads=8, nonlinear_message=True,
+               irreps_mlp_mid="768x0e+384x1e", alpha_drop=0.0, max_neighbors=500)
+AUX_CFG = dict(irreps_node_embedding="32x0e+16x0o+16x1e+16x1o", num_layers=2, irreps_sh="1x0e+1x1o", max_radius=5.0,
+               number_of_basis=32, fc_neurons=[64, 64], irreps_feature="64x0e+16x1e+16x1o",
+               irreps_head="8x0e+4x0o+4x1e+4x1o", num_heads=4, nonlinear_message=True,
+               irreps_mlp_mid="64x0e+16x0o+32x1e+16x1o", alpha_drop=0.0, use_auxiliary_task=True)
+
+
+def factory_kwargs(name):
+    if name == "equiformer_md17_dens":  # takes the constructor's keywords (md17/configs/equiformer_dens/*.yml)
+        return dict(irreps_in="64x0e", irreps_equivariant_inputs="1x0e+1x1e+1x2e", max_radius=5.0, number_of_basis=32,
+                    basis_type="exp", irreps_feature="512x0e+256x1e+128x2e", alpha_drop=0.0)
+    return dict(irreps_in="64x0e" if "md17" in name else "5x0e", radius=5.0, num_basis=32 if "md17" in name else 128)
+
+
+def param_table(model):
+    """["name:d0xd1..."] in registration order"""
+    return np.array(["%s:%s" % (n, "x".join(str(d) for d in p.shape)) for n, p in model.named_parameters()])
+
+
+def param_digest(model):
+    """sha256 over the names and the fp32 bytes of every parameter, in registration order (initial values bit for bit)"""
+    import hashlib
+    h = hashlib.sha256()
+    for n, p in model.named_parameters():
+        h.update(n.encode())
+        h.update(np.ascontiguousarray(p.detach().float().numpy()).tobytes())
+    return h.hexdigest()
+
+
+def full_size_input(name):
+    from equiformer_amd.synthetic import md17_aspirin_batch, qm9_like_batch
+    return md17_aspirin_batch(1, seed=1) if "md17" in name else qm9_like_batch(2, 12, side=5.5, seed=2)
+
+
+def run_full_size(model, name):
+    d = full_size_input(name)
+    if "md17" in name:
+        e, f = model(node_atom=d["z"], pos=d["pos"].double(), batch=d["batch"])
+        return dict(energy=e.detach().numpy(), forces=f.detach().numpy())
+    return dict(energy=model(f_in=None, pos=d["pos"].double(), batch=d["batch"], node_atom=d["z"]).detach().numpy())
+
+
+def otf_input():
+    """two periodic structures (10 atoms each, triclinic cells) for the on-the-fly graph case"""
+    rng = np.random.default_rng(3)
+    n, B = 10, 2
+    cell = torch.tensor([[[6.0, 0, 0], [1.0, 6.5, 0], [0, 0, 12.0]], [[7.0, 0, 0], [0, 6.0, 0], [0.5, 0, 11.0]]]).double()
+    pos = torch.tensor(rng.uniform(0, 6.0, size=(B * n, 3))).double()
+    return SimpleNamespace(pos=pos, batch=torch.arange(B).repeat_interleave(n), atomic_numbers=torch.tensor(rng.integers(1, 84, B * n)),
+                           tags=torch.tensor(rng.integers(0, 3, B * n)), cell=cell, natoms=torch.tensor([n] * B))
+
+
+def otf_oracle():
+    """the oracle's OC20 model of the on-the-fly case, weights filled by name (tests/golden/weights.py), fp32 values"""
+    from oracle import nets as onets
+    return fill_deterministic(onets.GraphAttentionTransformerOC20(**{k: v for k, v in OTF_CFG.items() if k != "max_neighbors"}), 5)
+
+
+def aux_oracle():
+    """the oracle's OC20 model with the E(3) auxiliary head, weights filled by name, fp32 values"""
+    from oracle import nets as onets
+    return fill_deterministic(onets.GraphAttentionTransformerOC20(**AUX_CFG), 1)
+
+
+def write_pin(reference="/root/reference", shims=None, log=print):
+    """Run the reference's own model code and record, in PIN: the outputs behind every golden fixture, every registered
+    factory's parameter table / initial-value digest / no-weight-decay set, and the outputs of the full-width and OC20 cases."""
+    R, _ = reference_outputs(reference, shims, log)
+    rnets = sys.modules["nets"]
+    arrs = {}
+    for tag, outs in R.items():
+        for k, v in outs.items():
+            arrs["out::%s::%s" % (tag, k)] = np.asarray(v)
+    rreg = sys.modules["nets.registry"]  # (`nets.registry` the ATTRIBUTE is ocpmodels' registry object after the star-imports)
+    names = sorted(rreg._model_entrypoints)
+    arrs["reg::names"] = np.array(names)
+    for name in names:
+        torch.manual_seed(7)
+        r = rnets.model_entrypoint(name)(**factory_kwargs(name))
+        arrs["reg::%s::params" % name] = param_table(r)
+        arrs["reg::%s::digest" % name] = np.array(param_digest(r))
+        arrs["reg::%s::no_wd" % name] = np.array(sorted(r.no_weight_decay()))
+        log("  registry %s: %d parameters" % (name, len(arrs["reg::%s::params" % name])))
+    for name, count in FULL_SIZE:
+        torch.manual_seed(3)
+        r = rnets.model_entrypoint(name)(**factory_kwargs(name))
+        arrs["full::%s::count" % name] = np.array(sum(p.numel() for p in r.parameters()))
+        arrs["full::%s::digest" % name] = np.array(param_digest(r))
+        for k, v in run_full_size(as_double(r), name).items():
+            arrs["full::%s::%s" % (name, k)] = v
+    from nets.graph_attention_transformer_oc20 import GraphAttentionTransformerOC20 as RefOC20
+    r = RefOC20(None, None, 1, use_pbc=True, otf_graph=True, **OTF_CFG)
+    copy_by_name(otf_oracle(), r)  # the oracle's deterministic weights (the product draws this model's init in another order)
+    data = otf_input()
+    arrs["otf::energy"] = as_double(r)(data).detach().numpy()
+    for k in ("edge_index", "cell_offsets", "neighbors"):  # the periodic graph the reference's own search produced
+        arrs["otf::" + k] = getattr(data, k).numpy()
+    r = RefOC20(None, None, 1, use_pbc=True, otf_graph=False, **AUX_CFG)
+    arrs["aux::params"] = param_table(r)
+    copy_by_name(aux_oracle(), r)
+    ins, _ = load_fixture("oc20_aux_small")
+    e, a = as_double(r)(_oc20_data(ins))
+    arrs["aux::energy"], arrs["aux::aux"] = e.detach().numpy(), a.detach().numpy()
+    np.savez_compressed(PIN, **arrs)
+    log("wrote %s (%d arrays)" % (PIN, len(arrs)))
+
+
+def load_pin():
+    z = np.load(PIN)
+    return {k: z[k] for k in z.files}
+
+
+def check_pinned(log=print):
+    """check_all() against the reference outputs recorded in PIN: -> {(tag, key): (fixture err, oracle err)}"""
+    pin = load_pin()
+    _, O = reference_outputs(log=log, with_reference=False)
+    errs = {}
+    for key in sorted(k for k in pin if k.startswith("out::")):
+        _, tag, k = key.split("::")
+        _, outs = load_fixture(tag)
+        errs[(tag, k)] = (rel(outs[k], pin[key]), rel(O[tag][k], pin[key]))
+        log("  %-18s %-14s fixture vs reference %.3e   oracle vs reference %.3e" % ((tag, k) + errs[(tag, k)]))
+    for tag, outs in O.items():
+        _, fouts = load_fixture(tag)
+        assert set(fouts) == set(outs) == {k for t, k in errs if t == tag}, (tag, sorted(fouts), sorted(outs))
+    missing = sorted(f[:-4] for f in os.listdir(HERE) if f.endswith(".npz") and f[:-4] not in O and f != os.path.basename(PIN))
     assert not missing, "fixtures without a reference run: %s" % missing
     return errs
 
@@ -217,7 +363,12 @@ def main():
     ap.add_argument("--reference", default="/root/reference", help="checkout of atomicarchitects/equiformer")
     ap.add_argument("--write", action="store_true", help="overwrite the out:: arrays with the reference's outputs")
     ap.add_argument("--real-deps", action="store_true", help="never use oracle/refshim (the real environment is installed)")
+    ap.add_argument("--pin", action="store_true", help="record the reference's outputs, parameter tables and initial-value "
+                    "digests in reference_pin.npz (what tests/test_reference_pin.py checks)")
     a = ap.parse_args()
+    if a.pin:
+        write_pin(a.reference, shims=False if a.real_deps else None)
+        return
     errs = check_all(a.reference, shims=False if a.real_deps else None, write=a.write)
     worst = max(max(v) for v in errs.values())
     print("worst relative difference vs the reference's own model code: %.3e (tolerance %.0e)" % (worst, TOL))

@@ -1,164 +1,115 @@
-"""The pin of the oracle: the REFERENCE'S OWN model code (/root/reference/nets, imported unchanged through the
-dependency stand-ins of oracle/refshim) executed on CPU in fp64 and compared with
+"""The pin of the oracle: the REFERENCE'S OWN model code (its nets/ package, imported unchanged through the dependency
+stand-ins of oracle/refshim) executed on CPU in fp64, as recorded in tests/golden/reference_pin.npz by
+`tests/golden/make_reference_golden.py --pin`, and compared with
 
   * every golden fixture of tests/golden/*.npz (which tests/golden/make_reference_golden.py --write produced from it),
   * the oracle restatement oracle/nets.py built with the same weights (copied BY NAME, both directions checked),
   * the product's host mirror equiformer_amd.nets: every registered factory name, every parameter name / shape and --
-    under the same torch seed -- every INITIAL VALUE, bit for bit (registry, names, init coupling).
+    under the same torch seed -- every INITIAL VALUE, bit for bit (registry, names, init coupling; the pin
+    holds a sha256 digest of the reference's initial values).
 
-Needs the reference checkout (/root/reference, or $EQF_REFERENCE); it does not exist on the GPU box, where these tests
-skip and tests/test_golden.py checks the same fixtures instead."""
+The full-width cases build the PRODUCT's model under the reference's seed, check that its initial values are the
+reference's (digest), and copy them into the oracle, whose fp64 outputs must equal the reference's recorded ones; the two
+OC20 cases ran the reference with the oracle's name-filled weights (tests/golden/weights.py), which the test fills again."""
 import os
 import sys
 import warnings
 
+import numpy as np
 import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 sys.path.insert(0, os.path.dirname(HERE))
-from oracle.refshim import load_reference_nets, reference_available  # noqa: E402
+import make_reference_golden as mrg  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not reference_available(), reason="no reference checkout (only in the build container)")
 warnings.filterwarnings("ignore", category=FutureWarning)
 
 
 @pytest.fixture(scope="module")
-def rnets():
-    return load_reference_nets()
+def pin():
+    return mrg.load_pin()
 
 
-def test_reference_package_is_the_unmodified_checkout(rnets):
-    import nets.graph_attention_transformer as g
-    import e3nn
-    from oracle import refshim
-    assert os.path.abspath(g.__file__).startswith(os.path.abspath(refshim.DEFAULT_REFERENCE))
-    assert os.path.abspath(e3nn.__file__).startswith(refshim.PKGS)  # the stand-in, not a real installation
-    assert callable(rnets.model_entrypoint)
-
-
-def test_fixtures_and_oracle_equal_the_reference_model_code(rnets):
-    import make_reference_golden as mrg
-    errs = mrg.check_all(log=lambda *a: None)
+def test_fixtures_and_oracle_equal_the_reference_model_code():
+    errs = mrg.check_pinned(log=lambda *a: None)
     assert len({t for t, _ in errs}) == 10  # every fixture family
     bad = {k: v for k, v in errs.items() if max(v) > mrg.TOL}
     assert not bad, bad
 
 
-def _factory_kwargs(name):
-    if name == "equiformer_md17_dens":  # takes the constructor's keywords (md17/configs/equiformer_dens/*.yml)
-        return dict(irreps_in="64x0e", irreps_equivariant_inputs="1x0e+1x1e+1x2e", max_radius=5.0, number_of_basis=32,
-                    basis_type="exp", irreps_feature="512x0e+256x1e+128x2e", alpha_drop=0.0)
-    return dict(irreps_in="64x0e" if "md17" in name else "5x0e", radius=5.0, num_basis=32 if "md17" in name else 128)
-
-
-def test_registry_names_parameters_and_initial_values_equal_the_reference(rnets):
-    rreg = sys.modules["nets.registry"]  # (`nets.registry` the ATTRIBUTE is ocpmodels' registry object after the star-imports)
+def test_registry_names_parameters_and_initial_values_equal_the_reference(pin):
     from equiformer_amd import nets as pnets
     from equiformer_amd.nets import registry as preg
-    ref_names = sorted(rreg._model_entrypoints)
+    ref_names = list(pin["reg::names"])
     assert len(ref_names) == 20
     assert set(ref_names) <= set(preg.list_models())
     for name in ref_names:
-        kw = _factory_kwargs(name)
         torch.manual_seed(7)
-        r = rnets.model_entrypoint(name)(**kw)
-        torch.manual_seed(7)
-        p = pnets.model_entrypoint(name)(**kw)
-        rp, pp = dict(r.named_parameters()), dict(p.named_parameters())
-        assert set(rp) == set(pp), (name, sorted(set(rp) ^ set(pp))[:6])
-        assert list(rp) == list(pp), name  # registration ORDER too: optimizer checkpoints index parameters by position
+        p = pnets.model_entrypoint(name)(**mrg.factory_kwargs(name))
+        rt, pt = list(pin["reg::%s::params" % name]), list(mrg.param_table(p))
+        rn, pn = [e.split(":")[0] for e in rt], [e.split(":")[0] for e in pt]
+        assert set(rn) == set(pn), (name, sorted(set(rn) ^ set(pn))[:6])
+        assert rn == pn, name  # registration ORDER too: optimizer checkpoints index parameters by position
+        assert rt == pt, (name, [(a, b) for a, b in zip(rt, pt) if a != b][:6])  # shapes
         if name == "equiformer_md17_dens":
             # the product builds this model on top of its MD17 class, so force_embed draws its random numbers later
             # than in the reference (:134): same names / shapes / order, another RNG stream
-            assert all(rp[k].shape == pp[k].shape for k in rp)
             continue
-        diff = [k for k in rp if rp[k].shape != pp[k].shape or not torch.equal(rp[k], pp[k])]
-        assert not diff, (name, diff[:6])
-        assert r.no_weight_decay() == p.no_weight_decay(), name
+        assert mrg.param_digest(p) == str(pin["reg::%s::digest" % name]), name  # every initial value, bit for bit
+        assert sorted(p.no_weight_decay()) == list(pin["reg::%s::no_wd" % name]), name
 
 
-@pytest.mark.parametrize("name,count", [("graph_attention_transformer_nonlinear_l2", 3_531_715),
-                                        ("graph_attention_transformer_nonlinear_exp_l2_md17", 3_496_001),
-                                        ("graph_attention_transformer_nonlinear_exp_l3_md17", 5_500_865)])
-def test_full_size_baseline_factories_oracle_equals_reference(rnets, name, count):
-    """BASELINE configs at full width through the reference's registry; the reference's own random initialisation is
-    copied into the oracle; fp64 forward (and forces) on a small batch."""
-    import make_reference_golden as mrg
+@pytest.mark.parametrize("name,count", list(mrg.FULL_SIZE))
+def test_full_size_baseline_factories_oracle_equals_reference(pin, name, count):
+    """BASELINE configs at full width through the registry; the reference's own random initialisation (= the product's
+    under the same seed, digest-checked) is copied into the oracle; fp64 forward (and forces) on a small batch."""
+    from equiformer_amd import nets as pnets
     from oracle import nets as onets
-    from equiformer_amd.synthetic import md17_aspirin_batch, qm9_like_batch
-    kw = _factory_kwargs(name)
+    kw = mrg.factory_kwargs(name)
     torch.manual_seed(3)
-    r = rnets.model_entrypoint(name)(**kw)
-    assert sum(p.numel() for p in r.parameters()) == count  # SURVEY KAT-4 (the paper's parameter counts)
+    p = pnets.model_entrypoint(name)(**kw)
+    assert int(pin["full::%s::count" % name]) == count  # SURVEY KAT-4 (the paper's parameter counts)
+    assert sum(q.numel() for q in p.parameters()) == count
+    assert mrg.param_digest(p) == str(pin["full::%s::digest" % name])
     o = onets.model_entrypoint(name)(**kw)
-    mrg.copy_by_name(r, o)
-    r, o = mrg.as_double(r), o.double().eval()
+    mrg.copy_by_name(p, o)
+    got = mrg.run_full_size(o.double().eval(), name)
     if "md17" in name:
-        d = md17_aspirin_batch(1, seed=1)
-        (er, fr), (eo, fo) = (m(node_atom=d["z"], pos=d["pos"].double(), batch=d["batch"]) for m in (r, o))
-        assert mrg.rel(fo.detach(), fr.detach()) < 1e-9
-    else:
-        d = qm9_like_batch(2, 12, side=5.5, seed=2)
-        er, eo = (m(f_in=None, pos=d["pos"].double(), batch=d["batch"], node_atom=d["z"]) for m in (r, o))
-    assert mrg.rel(eo.detach(), er.detach()) < 1e-10
+        assert mrg.rel(got["forces"], pin["full::%s::forces" % name]) < 1e-9
+    assert mrg.rel(got["energy"], pin["full::%s::energy" % name]) < 1e-10
 
 
-def test_oc20_full_width_on_the_fly_periodic_graph_oracle_equals_reference(rnets):
+def test_oc20_full_width_on_the_fly_periodic_graph_oracle_equals_reference(pin):
     """Config #5 (l1_256_nonlinear) through the reference's class with otf_graph=True / use_pbc=True: the reference's
-    _forward_otf_graph + _forward_use_pbc (..._oc20.py:267-302) drive the periodic search; the oracle gets the edges and
-    Cartesian offsets they produced."""
-    import make_reference_golden as mrg
-    from types import SimpleNamespace
-    from nets.graph_attention_transformer_oc20 import GraphAttentionTransformerOC20 as RefOC20
-    from oracle import nets as onets, pbc
-    import numpy as np
-    cfg = dict(irreps_node_embedding="256x0e+128x1e", num_layers=2, irreps_sh="1x0e+1x1e", max_radius=5.0, number_of_basis=128,
-               fc_neurons=[64, 64], irreps_feature="512x0e", irreps_head="32x0e+16x1e", num_heads=8, nonlinear_message=True,
-               irreps_mlp_mid="768x0e+384x1e", alpha_drop=0.0, max_neighbors=500)
-    torch.manual_seed(5)
-    r = RefOC20(None, None, 1, use_pbc=True, otf_graph=True, **cfg)
-    o = onets.GraphAttentionTransformerOC20(**{k: v for k, v in cfg.items() if k != "max_neighbors"})
-    mrg.copy_by_name(r, o)
-    r, o = mrg.as_double(r), o.double().eval()
-    rng = np.random.default_rng(3)
-    n, B = 10, 2
-    cell = torch.tensor([[[6.0, 0, 0], [1.0, 6.5, 0], [0, 0, 12.0]], [[7.0, 0, 0], [0, 6.0, 0], [0.5, 0, 11.0]]]).double()
-    pos = torch.tensor(rng.uniform(0, 6.0, size=(B * n, 3))).double()
-    batch = torch.arange(B).repeat_interleave(n)
-    data = SimpleNamespace(pos=pos, batch=batch, atomic_numbers=torch.tensor(rng.integers(1, 84, B * n)),
-                           tags=torch.tensor(rng.integers(0, 3, B * n)), cell=cell, natoms=torch.tensor([n] * B))
-    er = r(data)
-    ei, dist, off = pbc.get_pbc_distances(pos, data.edge_index, cell, data.cell_offsets, data.neighbors)
+    _forward_otf_graph + _forward_use_pbc (..._oc20.py:267-302) drove the periodic search; the oracle gets the edges and
+    Cartesian offsets they produced (recorded in the pin).  Both ran with the same name-filled weights."""
+    from oracle import pbc
+    o = mrg.otf_oracle().double().eval()
+    data = mrg.otf_input()
+    t = torch.as_tensor
+    ei, dist, off = pbc.get_pbc_distances(data.pos, t(pin["otf::edge_index"]), data.cell, t(pin["otf::cell_offsets"]),
+                                          t(pin["otf::neighbors"]))
     assert ei.shape[1] > 100
-    eo = o(data.atomic_numbers, data.tags, pos, batch, edge_index=ei, offsets=off)
-    assert mrg.rel(eo.detach(), er.detach()) < 1e-10
+    eo = o(data.atomic_numbers, data.tags, data.pos, data.batch, edge_index=ei, offsets=off)
+    assert mrg.rel(eo.detach(), pin["otf::energy"]) < 1e-10
 
 
-def test_oc20_e3_auxiliary_head_emits_1o_like_the_reference(rnets):
+def test_oc20_e3_auxiliary_head_emits_1o_like_the_reference(pin):
     """E(3) feature with 1o channels + use_auxiliary_task: the head's output irreps are 1x1o [ref: ..._oc20.py:184-186]
     (the oracle and the product had 1x1e hard-coded until round 3)."""
-    import make_reference_golden as mrg
-    from nets.graph_attention_transformer_oc20 import GraphAttentionTransformerOC20 as RefOC20
-    from oracle import nets as onets
     from equiformer_amd.nets.graph_attention_transformer_oc20 import GraphAttentionTransformerOC20 as ProdOC20
-    cfg = dict(irreps_node_embedding="32x0e+16x0o+16x1e+16x1o", num_layers=2, irreps_sh="1x0e+1x1o", max_radius=5.0,
-               number_of_basis=32, fc_neurons=[64, 64], irreps_feature="64x0e+16x1e+16x1o",
-               irreps_head="8x0e+4x0o+4x1e+4x1o", num_heads=4, nonlinear_message=True,
-               irreps_mlp_mid="64x0e+16x0o+32x1e+16x1o", alpha_drop=0.0, use_auxiliary_task=True)
-    torch.manual_seed(1)
-    r = RefOC20(None, None, 1, use_pbc=True, otf_graph=False, **cfg)
-    o = onets.GraphAttentionTransformerOC20(**cfg)
-    mrg.copy_by_name(r, o)
     # the product builds it too since round 4 (values against the oracle on the GPU: tests/test_gpu_oc20_heads.py): same
     # parameter names, shapes and order as the reference
-    prod = ProdOC20(None, None, 1, use_pbc=True, otf_graph=False, **cfg)
-    assert [(n, tuple(p.shape)) for n, p in prod.named_parameters()] == [(n, tuple(p.shape)) for n, p in r.named_parameters()]
-    r, o = mrg.as_double(r), o.double().eval()
+    prod = ProdOC20(None, None, 1, use_pbc=True, otf_graph=False, **mrg.AUX_CFG)
+    assert list(mrg.param_table(prod)) == list(pin["aux::params"])
+    o = mrg.aux_oracle()
+    assert list(mrg.param_table(o)) == list(pin["aux::params"])
+    o = o.double().eval()  # the weights the reference ran with (name-filled)
     ins, _ = mrg.load_fixture("oc20_aux_small")
     t = torch.as_tensor
-    er, ar = r(mrg._oc20_data(ins))
     eo, ao = o(t(ins["z"]), t(ins["tags"]), t(ins["pos"]).double(), t(ins["batch"]), edge_index=t(ins["edge_index"]),
                offsets=t(ins["offsets"]).double())
-    assert mrg.rel(eo.detach(), er.detach()) < 1e-10 and mrg.rel(ao.detach(), ar.detach()) < 1e-10
+    assert ao.shape[-1] == 3 and np.asarray(pin["aux::aux"]).shape == tuple(ao.shape)
+    assert mrg.rel(eo.detach(), pin["aux::energy"]) < 1e-10 and mrg.rel(ao.detach(), pin["aux::aux"]) < 1e-10

@@ -10,7 +10,7 @@ TAG=${1:-rX}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 nproc > $OUT/nproc.txt
-SHORT="--no-cpu-baseline --no-sub-records --repeats 1"
+SHORT="--full --no-cpu-baseline --no-sub-records --repeats 1"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o $TAG -- python bench.py --steps 7 --warmup 2 $SHORT > $OUT/bench_prof.json 2> $OUT/prof.err
 DB=$(find $OUT/prof -name '*.db' | head -1)
 [ -n "$DB" ] && python tools/rocpd_stats.py $DB --csv $OUT/kernel_stats.csv --top 80 > $OUT/kernel_stats.txt
@@ -24,7 +24,7 @@ python tools/pmc_bench.py $OUT $OUT/pmc_dominant.json > $OUT/pmc_summary.txt 2>&
 cat $OUT/pmc_summary.txt
 cp $OUT/pmc_dominant.json profiles/pmc_dominant.json
 find $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_mfma -name '*.csv' -size +2000k -delete
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 head -30 $OUT/kernel_stats.txt | cut -c1-90,112-160
 python -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """HBM traffic of the matrix-core kernels of bench.py's train step from two rocprofv3 PMC passes over bench.py itself:
 
-    rocprofv3 --pmc FETCH_SIZE -d <dir>/pmc_fetch -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE -d <dir>/pmc_write -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE -d <dir>/pmc_fetch -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE -d <dir>/pmc_write -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
     rocprofv3 --pmc SQ_INSTS_MFMA -d <dir>/pmc_mfma -- python bench.py ...   (optional: matrix instructions per launch -> mfma_busy)
     python tools/pmc_bench.py <dir> [profiles/pmc_dominant.json]
 
