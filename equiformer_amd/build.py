@@ -76,8 +76,7 @@ def build(force=False, verbose=True, out=None, extra_flags=(), only=None):
     if out is None and not force and not _stale():
         return LIB
     hipcc = os.environ.get("HIPCC", "hipcc")
-    # development builds: EQF_EXTRA_FLAGS="-DEQF_DEV_SWITCHES=1" (phase switches / cycle counters inside the sfc and gemm
-    # kernels, tools/sfc_exp.py, tools/gemm_exp.py) or "-DEQF_XTRACE=1" (in-kernel clock samples, tools/sfcx_trace.py)
+    # development builds: EQF_EXTRA_FLAGS="-D..." adds flags to every source (objects are rebuilt, see the .flags files below)
     dev = os.environ.get("EQF_EXTRA_FLAGS", "").split() + list(extra_flags)
     objs = []
     procs = []

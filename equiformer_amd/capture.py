@@ -53,7 +53,7 @@ class CapturedTrainStep:
         loss.backward()
         self.opt.step()
         # detached: a caller that keeps the loss of an EAGER step must not keep that step's autograd graph alive into a later
-        # capture (hipStreamEndCapture crashed with one alive: tools/capture_debug4.py, round 6)
+        # capture (hipStreamEndCapture crashed with one alive, round 6)
         return loss.detach()
 
     def _draw_seed(self):

@@ -22,20 +22,6 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-int g_gemm_exp = 0;
-
-// Development switches (phases of a kernel switched off, per-phase cycle counters) cost scalar instructions inside the hot
-// loops: they are compiled in only with -DEQF_DEV_SWITCHES=1 (EQF_EXTRA_FLAGS="-DEQF_DEV_SWITCHES=1" python -m
-// equiformer_amd.build); in the product build the eqf_*_debug_exp bits that act inside kernels are no-ops.
-#ifndef EQF_DEV_SWITCHES
-#define EQF_DEV_SWITCHES 0
-#endif
-#if EQF_DEV_SWITCHES
-#define GEMM_OFF(g, bit) ((g).exp & (bit))
-#else
-#define GEMM_OFF(g, bit) false
-#endif
-
 namespace {
 
 constexpr int BK = 32;
@@ -246,7 +232,6 @@ struct RowsArgs {
   int rows_per_tile;
   int accumulate;
   int vecA, vecB;
-  int exp;  // development aid (eqf_gemm_debug_exp): 1 no stores, 2 no MFMA
   DtpA dtp;
 };
 
@@ -260,7 +245,6 @@ struct RowsP {  // one problem of a grouped launch (A operand from memory)
   int rows_per_tile;
   int accumulate;
   int vecA, vecB;
-  int exp;
 };
 constexpr int MAX_GROUP = 8;
 struct RowsGroup {
@@ -336,10 +320,9 @@ __device__ __forceinline__ void gemm_rows_body(const ArgsT& g, const int bx, con
       else
         lbk.issue(g.B, n0, ncnt, k1, g.K, g.vecB);
     }
-    if (!GEMM_OFF(g, 2)) mma_step<TM, TN, SA, SB>(As, Bs, wm0, wn0, 0, BK, acc);
+    mma_step<TM, TN, SA, SB>(As, Bs, wm0, wn0, 0, BK, acc);
     __syncthreads();
   }
-  if (GEMM_OFF(g, 1)) return;
 
   const int lane = threadIdx.x & 63;
   const int r = lane & 31, hi = lane >> 5;
@@ -579,7 +562,7 @@ void launch_rows_cfg(const RowsArgs& a, hipStream_t st) {
 template <int AMODE, int BMODE>
 int launch_rows(RowsArgs& a, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0) return 0;
-  const int bn = (a.N > 64 && !(g_gemm_exp & 4)) ? 128 : (a.N > 32 ? 64 : 32);
+  const int bn = a.N > 64 ? 128 : (a.N > 32 ? 64 : 32);
   // 64-row tiles when 128-row tiles would leave most of the 256 CUs without a workgroup
   const int d = AMODE == A_DTP ? a.dtp.d3 : 1;
   const long tiles128 = (long)eqf_cdiv(a.M, (128 / d) * d) * eqf_cdiv(a.N, bn);
@@ -592,7 +575,6 @@ int launch_rows(RowsArgs& a, hipStream_t st) {
   } else {
     a.rows_per_tile = bm;
   }
-  a.exp = g_gemm_exp;
   char name[96];
   snprintf(name, sizeof name, "gemm_rows_%dx%d_%s_%s", bm, bn, AMODE == A_DTP ? "dtp" : "mem",
            BMODE == B_KN ? "kn" : "nk");
@@ -705,11 +687,6 @@ int build_dtp(const eqf_dtp_paths* P, int l3, const float* x, const float* coupl
 
 extern "C" {
 
-int eqf_gemm_debug_exp(int mask) {
-  g_gemm_exp = mask;
-  return 0;
-}
-
 int eqf_gemm_nn(const float* A, eqf_rows ra, const float* B, int ldb, float* C, eqf_rows rc, const float* bias, int M,
                 int N, int K, int accumulate, void* stream) {
   if (!A || !B || !C || ra.d < 1 || rc.d < 1) return EQF_E_BADARG;
@@ -777,7 +754,6 @@ int eqf_gemm_group(const eqf_gemm_desc* d, int n, void* stream) {
       P.M = d[i].M, P.N = d[i].N, P.K = d[i].K, P.accumulate = d[i].accumulate;
       P.vecA = rows_vec_ok(d[i].A, d[i].ra);
       P.vecB = aligned16(d[i].B) && d[i].ldb % 4 == 0;
-      P.exp = 0;
       P.rows_per_tile = 64;
       if (P.N > 32) bn_need = 64;
       flops += 2.0 * P.M * (double)P.N * P.K;

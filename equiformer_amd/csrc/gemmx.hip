@@ -55,11 +55,11 @@ struct GXP {          // one problem
   int vecA, vecB;
   int steps_per_split;
 };
+// (the bound allows 2 * GX_MAXP + 3 ints beside the problems; the group has GX_MAXP + 2: n and woff)
 static_assert(sizeof(GXP) * GX_MAXP + 4 * (2 * GX_MAXP + 3) <= 4000, "kernarg segment");
 struct GXGroup {
   int n;
-  int zoff[GX_MAXP + 1];  // one-wave-per-tile kernels (development switch): blockIdx.z -> (problem, K chunk)
-  // LDS-tiled kernels: ONE-dimensional grid, workgroup b belongs to problem i with woff[i] <= b < woff[i + 1] (entries past n
+  // ONE-dimensional grid, workgroup b belongs to problem i with woff[i] <= b < woff[i + 1] (entries past n
   // are INT_MAX).  A (max tiles m, max tiles n, problems) grid launched mostly EMPTY workgroups when the problems of a group
   // differ in shape -- 23 k workgroups for the ~1 200 of a 24-problem weight-gradient group, 146 us per launch.
   int woff[GX_MAXP + 1];
@@ -541,215 +541,18 @@ __global__ __launch_bounds__(256) void gemmx_tn_kernel(const GXGroup g_byval) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------ direct kernels (node rows)
-// The node-row linears (2 304 rows x (2l+1)) are not matrix work: ~12 us per launch whatever the matrix rate (fp32 MFMA 12.8 us,
-// split planes 12.3 us, tools/gemm_shapes.py).  Experiment of round 4, kept behind eqf_gemmx_dev_set(0, 0): ONE WAVE owns a
-// 32 x 32 output tile and issues the loads of a whole 128-deep K chunk (operand fragments straight in MFMA layout, no LDS, no
-// barrier) before it multiplies -- one round trip per chunk, ~1 000 independent waves per launch.  Measured: the same 12.7 us
-// (with loads behind per-lane bounds branches: 16 us, hipcc waits for them at the end of each branch); the floor of these
-// launches is neither the K loop nor the barriers.
-constexpr int GD_KC = 128;  // K chunk held in registers (8 fragments of 16)
-
-// Preconditions (checked on the host, else the LDS-tiled kernel runs): K a multiple of 16 and 16-byte-aligned rows, so that every
-// load is unconditional (rows / columns past the edge are clamped to a valid one and never stored): a load behind a per-lane
-// branch makes hipcc wait for it at the end of the branch, and the "all loads of the chunk in flight" is gone.
-template <int MODE, int BKIND>
-__global__ __launch_bounds__(64, 2) void gemmx_rows_direct_kernel(const GXGroup g_byval) {
-  KERNARG_IN_PLACE(GXGroup);
-  constexpr int NA = Planes<MODE>::A, NB = Planes<MODE>::W;
-  const GXP& P = g.p[blockIdx.z];
-  const int m0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-  if (m0 >= P.M || n0 >= P.N) return;
-  const int lane = threadIdx.x, r = lane & 31, hi = lane >> 5;
-  const int row = min(m0 + r, P.M - 1), col = min(n0 + r, P.N - 1);
-  const float* const ap = P.A.base + row_off2(row, P.A.d, P.A.ld, P.A.inner) + 8 * hi;
-  const float* const bp = BKIND == 1 ? P.B.base + (long)col * P.B.ld + 8 * hi : P.B.base + (long)(8 * hi) * P.B.ld + col;
-  f32x16 acc;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-  for (int kc = 0; kc < P.K; kc += GD_KC) {
-    float a[GD_KC / 16][8], b[GD_KC / 16][8];
-    const int kend = min(P.K - kc, GD_KC);
-#pragma unroll
-    for (int kt = 0; kt < GD_KC / 16; ++kt) {
-      if (16 * kt < kend) {  // uniform
-        const int k = kc + 16 * kt;
-        const float4 u0 = *reinterpret_cast<const float4*>(ap + k);
-        const float4 u1 = *reinterpret_cast<const float4*>(ap + k + 4);
-        a[kt][0] = u0.x, a[kt][1] = u0.y, a[kt][2] = u0.z, a[kt][3] = u0.w;
-        a[kt][4] = u1.x, a[kt][5] = u1.y, a[kt][6] = u1.z, a[kt][7] = u1.w;
-        if constexpr (BKIND == 1) {  // B [N, K]: k contiguous
-          const float4 w0 = *reinterpret_cast<const float4*>(bp + k);
-          const float4 w1 = *reinterpret_cast<const float4*>(bp + k + 4);
-          b[kt][0] = w0.x, b[kt][1] = w0.y, b[kt][2] = w0.z, b[kt][3] = w0.w;
-          b[kt][4] = w1.x, b[kt][5] = w1.y, b[kt][6] = w1.z, b[kt][7] = w1.w;
-        } else {  // B [K, N]: lane = column, eight rows down k (each a 128-byte run over the 32 columns)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) b[kt][j] = bp[(unsigned)(k + j) * (unsigned)P.B.ld];  // (32-bit offsets: one address register pair)
-        }
-      }
-    }
-#pragma unroll
-    for (int kt = 0; kt < GD_KC / 16; ++kt) {
-      if (16 * kt < kend) {  // uniform
-        bf16x8 pa[NA], pb[NB];
-        split_planes<NA>(a[kt], pa);
-        split_planes<NB>(b[kt], pb);
-        mma_terms<NA, NB>(pa, pb, acc);
-      }
-    }
-  }
-  if (n0 + r >= P.N) return;
-  const int ccol = n0 + r;
-  const float bv = P.bias ? P.bias[ccol] : 0.f;
-  const bool flat_c = P.C.d == 1;
-  const SmallDiv cdiv(P.C.d);
-  float* const cbase = const_cast<float*>(P.C.base);
-  const int rb = m0 + 4 * hi;
-  long off0;
-  int rem0 = 0;
-  if (flat_c) {
-    off0 = (long)rb * P.C.ld;
-  } else {
-    const int qb = rb / P.C.d;
-    rem0 = rb - qb * P.C.d;
-    off0 = (long)qb * P.C.ld;
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int dr = (q & 3) + 8 * (q >> 2);
-    if (rb + dr < P.M) {
-      long off;
-      if (flat_c) {
-        off = off0 + (long)dr * P.C.ld;
-      } else {
-        const int t = rem0 + dr, dq = cdiv.div(t);
-        off = off0 + (long)dq * P.C.ld + (long)(t - dq * P.C.d) * P.C.inner;
-      }
-      float* p = cbase + off + ccol;
-      float v = acc[q] + bv;
-      if (P.accumulate) v += *p;
-      *p = v;
-    }
-  }
-}
-
-// weight gradients: one wave per (32 x 32 tile of C, chunk of GD_KC reduction rows); both operands "lane = column, eight rows
-// down the reduction index"; column sums (bias gradients) from the fp32 registers; fp32 atomics into C.  Loads unconditional
-// (clamped row / column), rows past the end zeroed by a select.
-template <int MODE>
-__global__ __launch_bounds__(64, 2) void gemmx_tn_direct_kernel(const GXGroup g_byval) {
-  KERNARG_IN_PLACE(GXGroup);
-  constexpr int NA = Planes<MODE>::A;
-  int pi = 0;
-  while (pi + 1 < g.n && (int)blockIdx.z >= g.zoff[pi + 1]) ++pi;
-  const GXP& P = g.p[pi];
-  const int m0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-  if (m0 >= P.M || n0 >= P.N) return;
-  const int i0 = ((int)blockIdx.z - g.zoff[pi]) * GD_KC;
-  if (i0 >= P.K) return;
-  const int lane = threadIdx.x, r = lane & 31, hi = lane >> 5;
-  const int mcol = min(m0 + r, P.M - 1), ncol = min(n0 + r, P.N - 1);
-  const int kend = min(P.K - i0, GD_KC);
-  float a[GD_KC / 16][8], b[GD_KC / 16][8];
-  // two-level reduction rows i = q d + rem: (q, rem) of this lane's first row, then stepped (the two operands share d only by
-  // convention, so each keeps its own)
-  const int ifirst = i0 + 8 * hi;
-  int qa = ifirst / P.A.d, ra = ifirst - qa * P.A.d;
-  int qb = ifirst / P.B.d, rb = ifirst - qb * P.B.d;
-#pragma unroll
-  for (int kt = 0; kt < GD_KC / 16; ++kt) {
-    if (16 * kt < kend) {  // uniform
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = ifirst + 16 * kt + j;
-        const bool iv = i < P.K;
-        const long oa = iv ? (long)qa * P.A.ld + (long)ra * P.A.inner : 0;
-        const long ob = iv ? (long)qb * P.B.ld + (long)rb * P.B.inner : 0;
-        const float va = P.A.base[oa + mcol], vb = P.B.base[ob + ncol];
-        a[kt][j] = iv ? va : 0.f;
-        b[kt][j] = iv ? vb : 0.f;
-        ++ra, ++rb;
-        if (ra == P.A.d) ra = 0, ++qa;
-        if (rb == P.B.d) rb = 0, ++qb;
-      }
-      // the other half-wave's eight rows lie between this step's and the next step's
-      {
-        const int sa = ra + 8, sb = rb + 8;
-        const int da = sa / P.A.d, db = sb / P.B.d;
-        qa += da, ra = sa - da * P.A.d;
-        qb += db, rb = sb - db * P.B.d;
-      }
-    }
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-  float csa = 0.f, csb = 0.f, cca = 0.f, ccb = 0.f;  // (Kahan-compensated column sums, as in LoaderKS)
-#pragma unroll
-  for (int kt = 0; kt < GD_KC / 16; ++kt) {
-    if (16 * kt < kend) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float ya = a[kt][j] - cca, ta = csa + ya;
-        cca = (ta - csa) - ya, csa = ta;
-        const float yb = b[kt][j] - ccb, tb = csb + yb;
-        ccb = (tb - csb) - yb, csb = tb;
-      }
-      bf16x8 pa[NA], pb[NA];
-      split_planes<NA>(a[kt], pa);
-      split_planes<NA>(b[kt], pb);
-      mma_terms<NA, NA>(pa, pb, acc);
-    }
-  }
-  const bool mv = m0 + r < P.M, nv = n0 + r < P.N;
-  if (P.cs != nullptr) {
-    if (P.kind == 3 && blockIdx.y == 0) {
-      csa += __shfl_xor(csa, 32);
-      if (hi == 0 && mv) atomicAdd(P.cs + mcol, csa);
-    }
-    if (P.kind == 2 && blockIdx.x == 0) {
-      csb += __shfl_xor(csb, 32);
-      if (hi == 0 && nv) atomicAdd(P.cs + ncol, csb);
-    }
-  }
-  if (!nv) return;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int row = m0 + (q & 3) + 8 * (q >> 2) + 4 * hi;
-    if (row < P.M) atomicAdd(P.Cw + (long)row * P.ldc + ncol, acc[q]);
-  }
-}
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool rows_vec_ok(const float* base, const eqf_rows& r) { return aligned16(base) && (r.ld % 4 == 0) && (r.inner % 4 == 0); }
 
+// K steps per workgroup of a weight gradient at least (sweep: profiles/r04/r04_y_*).  Longer walks are NOT cheaper: the time of
+// these launches follows the steps per workgroup (8 / 16 / 24 / 48 / 96 steps: 25 / 40 / 57 / 101 / 192 us for the 480 x 480
+// node-row gradient), the 64 x 64 atomics per split do not show.  A constant, declared in the form tests/test_gemmx_plan.py
+// reads from this source.
+static int g_gemmx_tn_minsteps = 8;
+
 }  // namespace
 
-// development switch (eqf_gemmx_dev_set key 0): 0 = the one-wave-per-tile kernels for node-row problems, anything else = the
-// LDS-tiled kernels for every problem (the default: the two measure the same, tools/gemm_shapes.py, profiles/r04/r04_j_*)
-static int g_gemmx_no_direct = 1;
-static int g_gemmx_no_wide = 0;
-static int g_gemmx_tn_minsteps = 8;   // key 2: K steps per workgroup of a weight gradient at least (sweep: profiles/r04/r04_y_*)
-// key 1: 1 = the generic tiled kernel for the short-K, many-row problems too (A/B)
-
 extern "C" {
-
-int eqf_gemmx_dev_set(int key, int value) {
-  if (key == 0) {
-    g_gemmx_no_direct = value;
-    return 0;
-  }
-  if (key == 1) {
-    g_gemmx_no_wide = value;
-    return 0;
-  }
-  if (key == 2 && value >= 1) {
-    g_gemmx_tn_minsteps = value;
-    return 0;
-  }
-  return EQF_E_BADARG;
-}
 
 int eqf_gemmx_group(const eqf_gemm_desc* d, int n, int mode, void* stream) {
   if (!d || n < 1 || n > GX_MAXP || mode < 0 || mode > 2) return EQF_E_BADARG;
@@ -761,7 +564,7 @@ int eqf_gemmx_group(const eqf_gemm_desc* d, int n, int mode, void* stream) {
   static thread_local GXGroup G;
   for (int kind = 0; kind < 2; ++kind) {
     memset(&G, 0, sizeof G);
-    int maxm = 0, maxn = 0, big = 0, direct_ok = 1, wide_ok = 1, vec_ok = 1, wg = 0;
+    int maxm = 0, big = 0, wide_ok = 1, vec_ok = 1, wg = 0;
     double flops = 0, bytes = 0;
     for (int i = 0; i < n; ++i) {
       if (d[i].kind != kind || d[i].M <= 0 || d[i].N <= 0) continue;
@@ -775,31 +578,26 @@ int eqf_gemmx_group(const eqf_gemm_desc* d, int n, int mode, void* stream) {
       P.M = d[i].M, P.N = d[i].N, P.K = d[i].K, P.accumulate = d[i].accumulate, P.kind = kind;
       P.vecA = rows_vec_ok(d[i].A, d[i].ra);
       P.vecB = aligned16(d[i].B) && d[i].ldb % 4 == 0;
-      if (P.K % 16 != 0 || !P.vecA || (kind == 1 && !P.vecB)) direct_ok = 0;
       if (P.K % 4 != 0 || !P.vecA || (kind == 1 && !P.vecB)) vec_ok = 0;  // one unaligned problem: scalar loads for the group
       if (!(kind == 1 && P.K <= GW_K && P.K % 4 == 0 && P.vecA && P.vecB && P.M >= 8192 && P.N >= 2 * GX_T)) wide_ok = 0;
       if (eqf_cdiv(P.M, GX_T) > maxm) maxm = eqf_cdiv(P.M, GX_T);
-      if (eqf_cdiv(P.N, GX_T) > maxn) maxn = eqf_cdiv(P.N, GX_T);
       if (P.M >= 32768 / 2 + 1) big = 1;  // more than 16 k rows: edge rows
       flops += 2.0 * P.M * (double)P.N * P.K;
       bytes += 4.0 * ((double)P.M * P.K + (double)P.K * P.N + (double)P.M * P.N);
     }
     if (G.n == 0) continue;
-    // few rows (node-level linears): one wave per 32 x 32 tile, whole K chunks in flight; many rows (edge-level: the radial
-    // MLPs): the LDS-tiled kernel.  Timed under different names.
-    const bool direct = !big && direct_ok && !g_gemmx_no_direct;
-    const bool wide = kind == 1 && wide_ok && !g_gemmx_no_wide;
+    // node-level (few rows) and edge-level (the radial MLPs) launches are timed under different names.  One-wave-per-tile
+    // kernels for the node rows measured the same as the LDS-tiled ones (profiles/r04/r04_j_*) and were removed; their code is in
+    // git history.
+    const bool wide = kind == 1 && wide_ok;
     for (int i = G.n; i <= GX_MAXP; ++i) G.woff[i] = i == G.n ? wg : INT_MAX;
-    const dim3 grid = wide ? dim3(maxm, 1, G.n) : direct ? dim3(2 * maxm, 2 * maxn, G.n) : dim3(wg, 1, 1);
+    const dim3 grid = wide ? dim3(maxm, 1, G.n) : dim3(wg, 1, 1);
     const int pid = eqf_prof_begin(kind == 0 ? (big ? "gemmx_group_kn_edge" : "gemmx_group_kn_node")
                                              : (big ? "gemmx_group_nk_edge" : "gemmx_group_nk_node"), st, flops, bytes);
 #define GX_ROWS(M_)                                                                                              \
   do {                                                                                                           \
     if (wide) {                                                                                                  \
       hipLaunchKernelGGL((gemmx_rows_wide_kernel<M_>), grid, dim3(256), 0, st, G);                              \
-    } else if (direct) {                                                                                         \
-      if (kind == 0) hipLaunchKernelGGL((gemmx_rows_direct_kernel<M_, 0>), grid, dim3(64), 0, st, G);           \
-      else hipLaunchKernelGGL((gemmx_rows_direct_kernel<M_, 1>), grid, dim3(64), 0, st, G);                     \
     } else if (kind == 0) {                                                                                      \
       if (vec_ok) hipLaunchKernelGGL((gemmx_rows_kernel<M_, 0, true>), grid, dim3(256), 0, st, G);              \
       else hipLaunchKernelGGL((gemmx_rows_kernel<M_, 0, false>), grid, dim3(256), 0, st, G);                    \
@@ -817,8 +615,7 @@ int eqf_gemmx_group(const eqf_gemm_desc* d, int n, int mode, void* stream) {
   }
   {
     memset(&G, 0, sizeof G);
-    int maxm = 0, maxn = 0, z = 0, big = 0, zd = 0, wg = 0;
-    int zoff_d[GX_MAXP + 1];
+    int big = 0, wg = 0;
     double flops = 0, bytes = 0;
     for (int i = 0; i < n; ++i) {
       if (d[i].kind != 2 && d[i].kind != 3) continue;
@@ -831,42 +628,23 @@ int eqf_gemmx_group(const eqf_gemm_desc* d, int n, int mode, void* stream) {
       const int tiles = eqf_cdiv(P.M, GX_T) * eqf_cdiv(P.N, GX_T);
       const int total_steps = eqf_cdiv(P.K, GX_BK);
       int ksplit = 1024 / (tiles > 0 ? tiles : 1);
-      // at least g_gemmx_tn_minsteps K steps per workgroup.  Longer walks are NOT cheaper: the time of these launches follows
-      // the steps per workgroup (8 / 16 / 24 / 48 / 96 steps: 25 / 40 / 57 / 101 / 192 us for the 480 x 480 node-row gradient),
-      // the 64 x 64 atomics per split do not show
       const int max_split = eqf_cdiv(total_steps, g_gemmx_tn_minsteps);
       if (ksplit > max_split) ksplit = max_split;
       if (ksplit < 1) ksplit = 1;
       P.steps_per_split = eqf_cdiv(total_steps, ksplit);
       ksplit = eqf_cdiv(total_steps, P.steps_per_split);
-      G.zoff[G.n] = z;
-      z += ksplit;
       G.woff[G.n] = wg;
       wg += tiles * ksplit;
-      zoff_d[G.n] = zd;
-      zd += eqf_cdiv(P.K, GD_KC);
       G.n++;
-      if (eqf_cdiv(P.M, GX_T) > maxm) maxm = eqf_cdiv(P.M, GX_T);
-      if (eqf_cdiv(P.N, GX_T) > maxn) maxn = eqf_cdiv(P.N, GX_T);
       if (P.K >= 32768 / 2 + 1) big = 1;
       flops += 2.0 * P.M * (double)P.N * P.K;
       bytes += 4.0 * ((double)P.K * P.M + (double)P.K * P.N + (double)P.M * P.N);
     }
     if (G.n > 0) {
-      G.zoff[G.n] = z;
-      const bool direct = !big && !g_gemmx_no_direct;
-      if (direct) {
-        zoff_d[G.n] = zd;
-        for (int i = 0; i <= G.n; ++i) G.zoff[i] = zoff_d[i];
-      }
       for (int i = G.n; i <= GX_MAXP; ++i) G.woff[i] = i == G.n ? wg : INT_MAX;
-      const dim3 grid = direct ? dim3(2 * maxm, 2 * maxn, zd) : dim3(wg, 1, 1);
+      const dim3 grid(wg, 1, 1);
       const int pid = eqf_prof_begin(big ? "gemmx_group_tn_edge" : "gemmx_group_tn_node", st, flops, bytes);
-      if (direct) {
-        if (mode == 0) hipLaunchKernelGGL((gemmx_tn_direct_kernel<0>), grid, dim3(64), 0, st, G);
-        else if (mode == 1) hipLaunchKernelGGL((gemmx_tn_direct_kernel<1>), grid, dim3(64), 0, st, G);
-        else hipLaunchKernelGGL((gemmx_tn_direct_kernel<2>), grid, dim3(64), 0, st, G);
-      } else if (mode == 0) hipLaunchKernelGGL((gemmx_tn_kernel<0>), grid, dim3(256), 0, st, G);
+      if (mode == 0) hipLaunchKernelGGL((gemmx_tn_kernel<0>), grid, dim3(256), 0, st, G);
       else if (mode == 1) hipLaunchKernelGGL((gemmx_tn_kernel<1>), grid, dim3(256), 0, st, G);
       else hipLaunchKernelGGL((gemmx_tn_kernel<2>), grid, dim3(256), 0, st, G);
       eqf_prof_end(pid, st);

@@ -31,47 +31,21 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 extern __shared__ __attribute__((aligned(16))) float sfc_lds[];  // dynamic LDS of every kernel in this file
 
-// Development switches (phases of a kernel switched off, per-phase cycle counters) cost scalar instructions inside the hot
-// loops: they are compiled in only with -DEQF_DEV_SWITCHES=1 (EQF_EXTRA_FLAGS="-DEQF_DEV_SWITCHES=1" python -m
-// equiformer_amd.build); in the product build the eqf_*_debug_exp bits that act inside kernels are no-ops.
-#ifndef EQF_DEV_SWITCHES
-#define EQF_DEV_SWITCHES 0
-#endif
-#if EQF_DEV_SWITCHES
-#define SFC_OFF(g, bit) ((g).exp & (bit))
-#define SFC_DBG(g) ((g).dbg)
-#else
-#define SFC_OFF(g, bit) false
-#define SFC_DBG(g) ((unsigned long long*)nullptr)
-#endif
-
 namespace {
 
-unsigned long long* g_sfc_dbg = nullptr;  // set by eqf_sfc_debug_buffer (development aid)
 // workgroup ordering per kernel {fwd, bwd_data, bwd_weight}, see SfcOrder; measured (MI355X, E = 25 354): order 1 is
 // 8-12 % faster for bwd_weight, 0-6 % for bwd_data, and 0-14 % SLOWER for fwd (its workgroups of one degree share the
-// staged weight slabs, which the degree-major order keeps hot).  eqf_sfc_debug_order overrides all three for A/B runs.
-int g_sfc_order[3] = {0, 1, 1};
-// forward matrix step: exact-fp32 MFMA (false, the default) or split-precision bf16 x 6 on the matrix cores (true; f_mma6).
-// History: the split-precision step shipped in round 1, was found to return run-to-run different results at the bench size
-// (E = 25 k edges: two rows of an edge tile wrong by ~1e-2 in a few launches out of a hundred) and was switched off.
-// Root cause (round 2, profiles/r02/x6_investigation/): not the matrix step itself -- the PACKED-FP32 VALU instructions
-// (v_pk_fma_f32 / v_pk_mul_f32) hipcc emitted for the generation of the A tile return wrong values in lanes 48-63 now
-// and then while the co-resident workgroup's wave on the same SIMD runs the bf16 MFMAs.  The kernel variant that issues
-// bf16 MFMAs therefore contains no packed-FP32 instruction any more (x6_fmac / x6_mul / x6_sub): 0 wrong results in
-// 2 400 launches, full-size parity tests green with it.  Scalar instead of packed VALU work costs most of what the matrix
-// cores gained (interleaved A/B, tools/sfc_fwd_ab.py: sep_act 211.4 us vs 219.8 us with the fp32 step, sep_value 158.6 vs
-// 166.2; it was 203 vs 228 with the packed instructions): 0.6 % of a train step.  Not enough to change the default at
-// the end of a round whose first job was determinism: the exact-fp32 step stays the default, eqf_sfc_debug_exp(64)
-// selects the split-precision one (tests/test_gpu_fullsize.py keeps it bit-reproducible).
-bool g_sfc_x6_default = false;
-int g_sfc_exp = 0;  // development aid (eqf_sfc_debug_exp): bit mask that switches phases of the kernels OFF to time the rest
+// staged weight slabs, which the degree-major order keeps hot).
+constexpr int SFC_ORDER[3] = {0, 1, 1};
+// The forward matrix step is the exact-fp32 MFMA.  A split-precision step (bf16 x 6 on the matrix cores, free of packed-FP32
+// VALU instructions: DESIGN.md 3.1) measured 0.6 % of a train step faster and stayed off for determinism; it and the
+// paired 512-thread workgroups (measured slower) were removed, their code is in git history.
 
 using namespace sfc;
 
 __host__ inline SfcOrder make_order(int kernel, int nx, int ny, int& nblocks) {
   SfcOrder o;
-  o.mode = g_sfc_order[kernel], o.nx = nx, o.ny = ny;
+  o.mode = SFC_ORDER[kernel], o.nx = nx, o.ny = ny;
   o.per_xcd = (nx * ny + 7) / 8;
   nblocks = (o.mode == 1) ? 8 * o.per_xcd : nx * ny;
   return o;
@@ -102,9 +76,6 @@ struct SfcFwdArgs {
   SfcCommon c;
   const float* bias;   // [N1 of degree 0] or null
   const float* bias2;  // [N2] or null
-  unsigned long long* dbg;  // optional phase timers (development aid), may be null
-  int grp_floats;           // LDS floats per 256-thread group (paired workgroups)
-  int exp;                  // development aid: 1 no MFMA, 2 no generation, 4 no loads after the first slab, 8 no weight loads
   int nsplit[SFC_MAX_DEG], cps[SFC_MAX_DEG];
   SfcOrder ord;                                // nx = edge tiles, ny = (degree, column split) pairs
   signed char y_deg[16], y_split[16];
@@ -144,103 +115,25 @@ __device__ __forceinline__ void f_mma(const int (&aidx)[FT], const int (&bidx)[F
   }
 }
 
-// ---- split-precision matrix step (X6): fp32 operands, bf16 matrix cores ------------------------------------------
-// The fp32 MFMA runs on the VALU's FMA lanes, so it cannot overlap with the generation / addressing
-// work of the same kernel.  Here every fp32 operand value is split exactly into three bf16 terms x = x1 + x2 + x3
-// (v_cvt_pk_bf16_f32, two subtractions) and a . b is evaluated as the six products a1b1, a1b2, a2b1, a1b3, a3b1, a2b2
-// on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulation): error 3-4e-7 of the result scale, the same
-// as the fp32 GEMM (tools/bf16_split_error.py), at 12 x 32 cycles per 32 x 32 x 32 tile instead of 16 x 64 -- and on a
-// pipe of its own.  The A tile is then kept row-major in LDS ([row][k], stride X6_SA floats) so that a lane's eight
-// consecutive k values are two 16-byte reads.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int X6_SA = 36;  // floats per A row: 32 k + 4 pad (16-byte aligned rows, staggered banks)
-
-// Plain (non-packed) VALU instruction, whatever the optimiser would like to do with neighbouring lanes of a vector:
-// packed-FP32 instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) must not run in a kernel that also issues the
-// bf16 MFMAs -- see X6_NOTE below.
-__device__ __forceinline__ float x6_sub(float a, float b) {
-  float r;
-  asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ void x6_fmac(float& acc, float a, float b) { asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b)); }
-__device__ __forceinline__ float x6_mul(float a, float b) {
-  float r;
-  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8& p1, bf16x8& p2, bf16x8& p3) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h = (__bf16)v[j];
-    const float r1 = x6_sub(v[j], (float)h);
-    const __bf16 m = (__bf16)r1;
-    const float r2 = x6_sub(r1, (float)m);
-    p1[j] = h, p2[j] = m, p3[j] = (__bf16)r2;
-  }
-}
-
-template <int D3, int NT, int FT>
-__device__ __forceinline__ void f_mma6(const int (&arow)[FT], const int (&bcol)[FT], f32x16 (&acc)[FT]) {
-  constexpr int F_SB = f_sb(D3, FT);
-#pragma unroll
-  for (int kg = 0; kg < 2; ++kg) {  // two groups of 16 k per 32-channel slab
-    bf16x8 x1, x2, x3, y1, y2, y3;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      {
-        float av[8];
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>(&sfc_lds[arow[i] + 16 * kg]);
-        const f32x4 a1 = *reinterpret_cast<const f32x4*>(&sfc_lds[arow[i] + 16 * kg + 4]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) av[j] = a0[j], av[4 + j] = a1[j];
-        split3(av, x1, x2, x3);
-      }
-      {
-        float bw[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bw[j] = sfc_lds[bcol[i] + (16 * kg + j) * F_SB];
-        split3(bw, y1, y2, y3);
-      }
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, y2, acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, y3, acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, y1, acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, y2, acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, y1, acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, y1, acc[i], 0, 0, 0);
-    }
-  }
-}
-
-// PAIR: the workgroup has 512 threads = two independent 256-thread groups working on neighbouring edge tiles with
-// their own LDS partitions, run in ANTI-PHASE through the shared barriers: while one group's waves issue the MFMAs of
-// slab s, the other group's waves (the co-resident wave of every SIMD) wait for loads, generate the next A tile on the
-// VALU and write LDS.  Two free-running 256-thread workgroups per CU do the same work with the same resources, but
-// measured additively (MFMA 120 us + loads 45 + generation 30 + fixed 66 of 246 us: tools/sfc_exp.py): nothing forces
-// their matrix-pipe and memory phases apart.
-template <int D3, int MAXD, bool PAIR, bool X6>
+template <int D3, int MAXD>
 __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const int b) {
   constexpr int ROWS = F_TE * D3, RT = ROWS / 32, SA = ROWS + 1;
-  constexpr int A_FLOATS = X6 ? ROWS * X6_SA : 32 * SA;  // A tile: [row][k] (X6) or [k][row]
   constexpr int FT = (MAXD <= 5) ? 3 : F_MAXT;  // accumulator tiles per wave (host: `ft`)
   constexpr int CTCAP = f_ctcap(D3, FT), F_SB = f_sb(D3, FT);
   const SfcDeg& D = g.c.deg[di];
   const int nsplit = g.nsplit[di];
-  const int grp = PAIR ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;
-  const int xt = b / nsplit, ns = b - xt * nsplit;
-  const int tile = PAIR ? 2 * xt + grp : xt;
+  const int tile = b / nsplit, ns = b - tile * nsplit;
   int e0 = tile * F_TE;
   int ecnt = min(F_TE, g.c.E - e0);
-  if (ecnt <= 0) ecnt = 0, e0 = 0;  // odd tile count: the idle group runs along (barriers) on row 0 and stores nothing
+  if (ecnt <= 0) ecnt = 0, e0 = 0;
   const int ncol0 = ns * g.cps[di];
   const int ncols = min(g.cps[di], D.Ncat - ncol0);
   const int CT = ncols >> 5;
-  // LDS partition of this group (float offsets into sfc_lds)
-  const int AS0 = grp * g.grp_floats, BS0 = AS0 + A_FLOATS, MT0 = BS0 + 32 * F_SB;
+  // LDS layout (float offsets into sfc_lds): A tile [k][row], weight tile, coupling tile
+  constexpr int BS0 = 32 * SA, MT0 = BS0 + 32 * F_SB;
   const int m_len = D.m_len;
 
-  const int t = PAIR ? ((int)threadIdx.x & 255) : (int)threadIdx.x;
+  const int t = (int)threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lane = t & 63, r = lane & 31, hi = lane >> 5;
 
@@ -258,13 +151,8 @@ __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const
     const int ct = tt / RT, rt = tt - ct * RT;
     aoff[i] = rt * 32;
     boff[i] = ct * 32;
-    if (X6) {  // lane = (row r of the tile, k half hi): eight consecutive k of its row / its column
-      aidx[i] = AS0 + (aoff[i] + r) * X6_SA + 8 * hi;
-      bidx[i] = BS0 + (8 * hi) * F_SB + boff[i] + r;
-    } else {
-      aidx[i] = AS0 + hi * SA + r + aoff[i];
-      bidx[i] = BS0 + hi * F_SB + r + boff[i];
-    }
+    aidx[i] = hi * SA + r + aoff[i];
+    bidx[i] = BS0 + hi * F_SB + r + boff[i];
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[i][q] = 0.f;
   }
@@ -317,7 +205,6 @@ __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const
     // column blocks beyond CT re-read the last valid block (their LDS columns are never used): no guards, no
     // dynamic indexing of bv
     const int wk = s * 32 + (t >> 3);  // row of the weight matrices
-    if (!SFC_OFF(g, 8))
 #pragma unroll
     for (int j = 0; j < CTCAP; ++j) {
       const int c = ncol0 + 32 * (j < CT ? j : CT - 1);  // 32-column block: entirely main or entirely second consumer
@@ -325,54 +212,28 @@ __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const
       bv[j] = *reinterpret_cast<const f32x4*>(wp + 4 * (t & 7));
     }
   };
-  const int awb = AS0 + (4 * c4) * SA + eg;
+  const int awb = (4 * c4) * SA + eg;
   const int mrow = MT0 + eg * m_len;
   auto gen = [&](auto tag) __attribute__((always_inline)) {
     constexpr int D1 = decltype(tag)::value;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int mp = mrow + (32 * q) * m_len + s_mo;
-      f32x4 wm;
-      if (X6) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) wm[c] = x6_mul(wv[q][c], emask[q]);
-      } else {
-        wm = wv[q] * emask[q];
-      }
+      const f32x4 wm = wv[q] * emask[q];
 #pragma unroll
       for (int m3 = 0; m3 < D3; ++m3) {
-        if (X6) {
-          // X6_NOTE: scalar VALU instructions only.  With the vector expression below hipcc emits v_pk_fma_f32 /
-          // v_pk_mul_f32, and on MI355X a packed-FP32 instruction of this wave returns a wrong result in lanes 48-63
-          // every now and then while the OTHER wave of its SIMD (the co-resident workgroup) runs the bf16 MFMA step:
-          // measured with the same registers fed twice to the same expression (tools/sfc_race.py, profiles/r02/
-          // x6_investigation/: 8 differing evaluations per wrong output row, none with one workgroup per CU, none with
-          // the fp32 MFMA, none with these scalar instructions; LDS contents and prefetched registers verified intact).
-          float ac[4] = {0.f, 0.f, 0.f, 0.f};
+        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int i = 0; i < D1; ++i) {
-            const float m = sfc_lds[mp + i * D3 + m3];
+        for (int i = 0; i < D1; ++i) a += xv[q][i] * sfc_lds[mp + i * D3 + m3];
+        a *= wm;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) x6_fmac(ac[c], xv[q][i][c], m);
-          }
-          f32x4 a;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) a[c] = x6_mul(ac[c], wm[c]);
-          *reinterpret_cast<f32x4*>(&sfc_lds[AS0 + (m3 * F_TE + eg + 32 * q) * X6_SA + 4 * c4]) = a;
-        } else {
-          f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int i = 0; i < D1; ++i) a += xv[q][i] * sfc_lds[mp + i * D3 + m3];
-          a *= wm;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) sfc_lds[awb + c * SA + 32 * q + m3 * F_TE] = a[c];
-        }
+        for (int c = 0; c < 4; ++c) sfc_lds[awb + c * SA + 32 * q + m3 * F_TE] = a[c];
       }
     }
   };
   const int bwp = BS0 + (t >> 3) * F_SB + 4 * (t & 7);
   auto commit = [&]() __attribute__((always_inline)) {
-    if (!SFC_OFF(g, 2)) switch (s_d1) {
+    switch (s_d1) {
       case 1: gen(IC<1>()); break;
       case 3: gen(IC<3>()); break;
       case 5: gen(IC<(MAXD >= 5 ? 5 : 1)>()); break;
@@ -382,14 +243,6 @@ __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const
     for (int j = 0; j < CTCAP; ++j) *reinterpret_cast<f32x4*>(&sfc_lds[bwp + 32 * j]) = bv[j];
   };
 
-  unsigned long long t_mark = SFC_DBG(g) ? __builtin_amdgcn_s_memtime() : 0;
-  auto tick = [&](int slot) __attribute__((always_inline)) {
-    if (SFC_DBG(g)) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      if (t == 0) atomicAdd(SFC_DBG(g) + slot, now - t_mark);
-      t_mark = now;
-    }
-  };
   issue(0);
   // coupling tile: Mt[el][j] = coupling[e0+el, m_base + j]; rows of edges beyond the graph are zero.  Loads are
   // unconditional (clamped addresses) and batched: a one-element-per-iteration loop compiles to load / s_waitcnt
@@ -414,40 +267,20 @@ __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const
     }
   }
   __syncthreads();
-  tick(0);  // prologue
-  if (PAIR && grp == 1) __syncthreads();  // half a slab step behind group 0 from here on
   const int nslab = D.nslab;
   for (int s = 0; s < nslab; ++s) {
     commit();
-    tick(1);  // wait for the prefetched inputs + generation + LDS writes
     __syncthreads();
-    tick(2);  // barrier
-    if (s + 1 < nslab && !SFC_OFF(g, 4)) issue(s + 1);
-    tick(3);  // issue of the next slab's loads
-    if (!SFC_OFF(g, 1)) {
-      if constexpr (X6) {
-        switch (NT) {
-          case 1: f_mma6<D3, 1, FT>(aidx, bidx, acc); break;
-          case 2: f_mma6<D3, 2, FT>(aidx, bidx, acc); break;
-          case 3: f_mma6<D3, 3, FT>(aidx, bidx, acc); break;
-          default:
-            if constexpr (FT >= 4) f_mma6<D3, 4, FT>(aidx, bidx, acc);
-            break;
-        }
-      } else {
-        switch (NT) {
-          case 1: f_mma<D3, 1, FT>(aidx, bidx, acc); break;
-          case 2: f_mma<D3, 2, FT>(aidx, bidx, acc); break;
-          case 3: f_mma<D3, 3, FT>(aidx, bidx, acc); break;
-          default:
-            if constexpr (FT >= 4) f_mma<D3, 4, FT>(aidx, bidx, acc);
-            break;
-        }
-      }
+    if (s + 1 < nslab) issue(s + 1);
+    switch (NT) {
+      case 1: f_mma<D3, 1, FT>(aidx, bidx, acc); break;
+      case 2: f_mma<D3, 2, FT>(aidx, bidx, acc); break;
+      case 3: f_mma<D3, 3, FT>(aidx, bidx, acc); break;
+      default:
+        if constexpr (FT >= 4) f_mma<D3, 4, FT>(aidx, bidx, acc);
+        break;
     }
-    tick(4);  // MFMA loop
     __syncthreads();
-    tick(5);  // barrier
   }
 
   // epilogue: row = m3 * 64 + el ; column c of the concatenated output
@@ -475,21 +308,20 @@ __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const
       if (el < ecnt) base[(long)(e0 + el) * ld + coff + m3 * mstride] = acc[i][q] + bvl;
     }
   }
-  if (PAIR && grp == 0) __syncthreads();  // the barrier that ends group 1's last MFMA phase
 }
 
-template <int MAXD, bool PAIR, bool X6 = false>
-__global__ __launch_bounds__((PAIR ? 512 : 256), (PAIR || MAXD > 5 ? 1 : 2)) void sfc_fwd_kernel(const SfcFwdArgs g) {
+template <int MAXD>
+__global__ __launch_bounds__(256, (MAXD > 5 ? 1 : 2)) void sfc_fwd_kernel(const SfcFwdArgs g) {
   int tile, y;
   if (!order_xy(g.ord, blockIdx.x, tile, y)) return;
   const int di = g.y_deg[y];
   const int b = tile * g.nsplit[di] + g.y_split[y];
   switch (g.c.deg[di].d3) {
-    case 1: f_block<1, MAXD, PAIR, X6>(g, di, b); break;
-    case 3: f_block<3, MAXD, PAIR, X6>(g, di, b); break;
-    case 5: f_block<5, MAXD, PAIR, X6>(g, di, b); break;
+    case 1: f_block<1, MAXD>(g, di, b); break;
+    case 3: f_block<3, MAXD>(g, di, b); break;
+    case 5: f_block<5, MAXD>(g, di, b); break;
     default:
-      if constexpr (MAXD >= 7) f_block<7, MAXD, PAIR, X6>(g, di, b);
+      if constexpr (MAXD >= 7) f_block<7, MAXD>(g, di, b);
       break;
   }
 }
@@ -732,8 +564,6 @@ struct SfcBwdArgs {
   int dt_floats;  // LDS partition
   int full_m;     // the LDS coupling block holds whole coupling rows (mt_len == m_ld, mt_off == m_off)
   SfcOrder ord;   // nx = edge tiles, ny = chunk groups
-  int exp;        // development aid: 1 no MFMA loop, 2 no register epilogue, 4 no d_out staging after the first
-  unsigned long long* dbg;  // optional phase timers (cycles of wave 0 / lane 0 of every workgroup), may be null
   SfcBGroup grp[B_MAXGRP];
 };
 
@@ -756,14 +586,6 @@ __device__ __forceinline__ void b_block(const SfcBwdArgs& g, const SfcBGroup& G,
   const int el0 = 16 * eh + 4 * kg;    // first of this lane's 4 edges
   const int mt_len = G.mt_len;
 
-  unsigned long long t_mark = SFC_DBG(g) ? __builtin_amdgcn_s_memtime() : 0;
-  auto tick = [&](int slot) __attribute__((always_inline)) {
-    if (SFC_DBG(g)) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      if (t == 0) atomicAdd(SFC_DBG(g) + slot, now - t_mark);
-      t_mark = now;
-    }
-  };
   unsigned eo[4];   // clamped global edge index of this lane's edges
   bool ev[4];
 #pragma unroll
@@ -828,7 +650,6 @@ __device__ __forceinline__ void b_block(const SfcBwdArgs& g, const SfcBGroup& G,
     }
   }
   const float* const mrow = Mt + el0 * mt_len;
-  tick(0);  // prologue: x loads issued, coupling tile staged
 
   int staged_deg = -1;
   auto path = [&](auto tag, const SfcBPath& P, const int pi) __attribute__((always_inline)) {
@@ -874,7 +695,7 @@ __device__ __forceinline__ void b_block(const SfcBwdArgs& g, const SfcBGroup& G,
         // fragments of the first two k blocks (segment lengths are multiples of 32): in flight across the staging
         f32x4 bA = *reinterpret_cast<const f32x4*>(rowA + kc0);
         f32x4 bB = *reinterpret_cast<const f32x4*>(rowA + kc0 + 16);
-        if (!(nchunk == 1 && staged_deg == P.deg) && !(SFC_OFF(g, 4) && staged_deg >= 0)) {
+        if (!(nchunk == 1 && staged_deg == P.deg)) {
           __syncthreads();  // readers of the previous Dt contents are done
           // stage Dt[k][row] = d_out[e0 + el, m3, kc0 + k],  row = m3*32 + el.  A wave step covers 16 float4 columns x
           // 4 rows; all loads of a group of column blocks are issued before the first LDS write.
@@ -912,7 +733,6 @@ __device__ __forceinline__ void b_block(const SfcBwdArgs& g, const SfcBGroup& G,
           }
           staged_deg = P.deg;
           __syncthreads();
-          tick(1);  // staging of a d_out tile
         }
         const float* ap = Dt + (4 * kg) * SD + 16 * eh + j;
         // Two k blocks per iteration with statically named ping-pong registers (no register rotation, no copies): the
@@ -966,16 +786,14 @@ __device__ __forceinline__ void b_block(const SfcBwdArgs& g, const SfcBGroup& G,
           }
           if (kb < kb1) pair(bA, bB, kb);  // segment lengths are multiples of 32: at most one pair is left
         };
-        if (!SFC_OFF(g, 1)) seg(0, endA, rowA);
-        if (endA < kcn && !SFC_OFF(g, 1)) {
+        seg(0, endA, rowA);
+        if (endA < kcn) {
           bA = *reinterpret_cast<const f32x4*>(w2row + kc0 + endA);
           bB = *reinterpret_cast<const f32x4*>(w2row + kc0 + endA + 16);
           seg(endA, kcn, w2row);
         }
       }
-      tick(2);  // MFMA loop
       // DTP backward contraction in registers: this lane holds d_mid[m3][edge el0+q][channel 32c + ch]
-      if (!SFC_OFF(g, 2))
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float gw = 0.f;
@@ -1003,7 +821,6 @@ __device__ __forceinline__ void b_block(const SfcBwdArgs& g, const SfcBGroup& G,
         }
         if (g.dw && ev[q]) g.dw[(long)eo[q] * g.c.w_ld + P.w_off + 32 * c + ch] = gw;
       }
-      tick(3);  // register epilogue
     };
     // a real loop (not unrolled) around a static dispatch: keeps the chunks' live ranges apart
 #pragma unroll 1
@@ -1034,7 +851,6 @@ __device__ __forceinline__ void b_block(const SfcBwdArgs& g, const SfcBGroup& G,
 #pragma unroll
         for (int i = 0; i < D1; ++i) g.dx[(long)eo[q] * g.c.x_ld + G.x_off + 32 * c + i * G.x_mul + ch] = gx[c][q][i];
       }
-  tick(4);  // dx stores
 }
 
 // One launch covers every (input degree, chunk group) flavour: the flavours have different costs, and a single large
@@ -1059,27 +875,6 @@ __global__ __launch_bounds__(256, (MAXD <= 5 ? 2 : 1)) void sfc_bwd_kernel(const
 
 extern "C" {
 
-/* development aid (not declared in the public header): 8 x u64 device counters the data-gradient kernel adds its
- * per-phase cycle counts to; NULL disables */
-int eqf_sfc_debug_order(int mode) {
-  if (mode < -1 || mode > 2) return EQF_E_BADARG;
-  g_sfc_order[0] = mode < 0 ? 0 : mode;  // -1: defaults
-  g_sfc_order[1] = g_sfc_order[2] = mode < 0 ? 1 : mode;
-  return 0;
-}
-
-int eqf_sfc_debug_x6_default(void) { return g_sfc_x6_default ? 1 : 0; }
-
-int eqf_sfc_debug_exp(int mask) {
-  g_sfc_exp = mask;
-  return 0;
-}
-
-int eqf_sfc_debug_buffer(void* p) {
-  g_sfc_dbg = (unsigned long long*)p;
-  return 0;
-}
-
 int eqf_sfc_fwd(const float* x, const float* coupling, const float* w, const eqf_dtp_paths* paths,
                 const float* const* Wl, const float* bias0, const float* W2, const float* bias2, float* out1,
                 const eqf_irreps* out1_irreps, float* out2, int n2, int E, void* stream) {
@@ -1090,15 +885,10 @@ int eqf_sfc_fwd(const float* x, const float* coupling, const float* w, const eqf
   if (E <= 0) return 0;
   A.bias = bias0;
   A.bias2 = bias2;
-  A.dbg = g_sfc_dbg;
-  A.exp = g_sfc_exp;
   int md = max_d1(A.c);
   for (int d = 0; d < A.c.ndeg; ++d) md = A.c.deg[d].d3 > md ? A.c.deg[d].d3 : md;
   const int ft = md <= 5 ? 3 : F_MAXT;
   const int ntile = eqf_cdiv(E, F_TE);
-  // matrix step: 1 = split-precision bf16 x 6 on the matrix cores (f_mma6), 0 = exact-fp32 MFMA (development switch
-  // 64 of eqf_sfc_debug_exp selects the other one for A/B runs)
-  const bool x6 = md <= 5 && ((g_sfc_exp & 64) ? !g_sfc_x6_default : g_sfc_x6_default);
   size_t lds = 0;
   int ny = 0;
   for (int d = 0; d < A.c.ndeg; ++d) {
@@ -1116,18 +906,14 @@ int eqf_sfc_fwd(const float* x, const float* coupling, const float* w, const eqf
       A.y_deg[ny] = (signed char)d, A.y_split[ny] = (signed char)k;
       ++ny;
     }
-    const size_t a_floats = x6 ? (size_t)F_TE * D.d3 * X6_SA : (size_t)32 * (F_TE * D.d3 + 1);
+    const size_t a_floats = (size_t)32 * (F_TE * D.d3 + 1);
     const size_t need = sizeof(float) * (a_floats + 32 * f_sb(D.d3, ft) + (size_t)F_TE * D.m_len);
     if (need > lds) lds = need;
   }
   if (lds > SFC_LDS_LIMIT) return EQF_E_UNSUPPORTED;
   lds = (lds + 15) & ~(size_t)15;
-  // paired workgroups measured SLOWER than free-running ones (sep_act 297 vs 230 us, tools/sfc_exp.py): kept behind the
-  // development switch only
-  const bool pair = md <= 5 && !x6 && 2 * lds <= SFC_LDS_LIMIT && (g_sfc_exp & 16);
-  A.grp_floats = (int)(lds / sizeof(float));
   int blk = 0;
-  A.ord = make_order(0, pair ? eqf_cdiv(ntile, 2) : ntile, ny, blk);
+  A.ord = make_order(0, ntile, ny, blk);
 
   hipStream_t st = (hipStream_t)stream;
   const int pid = eqf_prof_begin("sfc_fwd", st, sfc_flops(A.c), sfc_bytes(A.c));
@@ -1138,19 +924,12 @@ int eqf_sfc_fwd(const float* x, const float* coupling, const float* w, const eqf
   (void)hipGetDevice(&dev_id);
   bool& attr_set = attr_done[dev_id & 63];
   if (!attr_set) {
-    hipFuncSetAttribute((const void*)sfc_fwd_kernel<5, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SFC_LDS_LIMIT);
-    hipFuncSetAttribute((const void*)sfc_fwd_kernel<5, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SFC_LDS_LIMIT);
-    hipFuncSetAttribute((const void*)sfc_fwd_kernel<7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SFC_LDS_LIMIT);
-    hipFuncSetAttribute((const void*)sfc_fwd_kernel<5, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        SFC_LDS_LIMIT);
+    hipFuncSetAttribute((const void*)sfc_fwd_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, SFC_LDS_LIMIT);
+    hipFuncSetAttribute((const void*)sfc_fwd_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, SFC_LDS_LIMIT);
     attr_set = true;
   }
-  if (x6 && !pair)
-    hipLaunchKernelGGL((sfc_fwd_kernel<5, false, true>), dim3(blk), dim3(256), (g_sfc_exp & 32) ? (size_t)100 * 1024 : lds, st, A);
-  else if (pair) hipLaunchKernelGGL((sfc_fwd_kernel<5, true>), dim3(blk), dim3(512), 2 * lds, st, A);
-  else if (md <= 5)
-    hipLaunchKernelGGL((sfc_fwd_kernel<5, false>), dim3(blk), dim3(256), (g_sfc_exp & 32) ? (size_t)100 * 1024 : lds, st, A);
-  else hipLaunchKernelGGL((sfc_fwd_kernel<7, false>), dim3(blk), dim3(256), lds, st, A);
+  if (md <= 5) hipLaunchKernelGGL(sfc_fwd_kernel<5>, dim3(blk), dim3(256), lds, st, A);
+  else hipLaunchKernelGGL(sfc_fwd_kernel<7>, dim3(blk), dim3(256), lds, st, A);
   eqf_prof_end(pid, st);
   EQF_CHECK_LAUNCH();
   return 0;
@@ -1232,8 +1011,6 @@ int eqf_sfc_bwd_data(const float* x, const float* coupling, const float* w, cons
   if (rc) return rc;
   if (E <= 0) return 0;
   A.dx = dx, A.dw = (w ? dw : nullptr), A.dM = d_coupling;
-  A.dbg = g_sfc_dbg;
-  A.exp = g_sfc_exp;
   // groups = (input segment, 32-channel chunk); paths sorted by output degree so that a staged d_out tile is shared
   A.ngrp = 0;
   int d3max = 1, mtmax = 0;
@@ -1317,7 +1094,7 @@ int eqf_sfc_bwd_data(const float* x, const float* coupling, const float* w, cons
       hipFuncSetAttribute((const void*)sfc_bwd_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, SFC_LDS_LIMIT);
       attr5 = true;
     }
-    hipLaunchKernelGGL(sfc_bwd_kernel<5>, grid, dim3(256), (g_sfc_exp & 32) ? (size_t)100 * 1024 : lds, st, A);
+    hipLaunchKernelGGL(sfc_bwd_kernel<5>, grid, dim3(256), lds, st, A);
   } else {
     static bool attr7_done[64] = {};
     int dev7 = 0;

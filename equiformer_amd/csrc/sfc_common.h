@@ -55,9 +55,7 @@ struct SfcCommon {
 struct SfcOrder {
   int mode, nx, ny, per_xcd;
 };
-#ifndef X_LPT_BATCH
-#define X_LPT_BATCH 8  // tiles per XCD and batch of order mode 4
-#endif
+constexpr int X_LPT_BATCH = 8;  // tiles per XCD and batch of order mode 4
 // false: surplus workgroup of the padded grid
 __device__ __forceinline__ bool order_xy(const SfcOrder& o, int b, int& x, int& y) {
   if (o.mode == 0) {

@@ -29,21 +29,6 @@ extern __shared__ __attribute__((aligned(16))) float sw_lds[];
 namespace {
 using namespace sfc;
 
-// development: -DEQF_W_TRACE=1 prints the cycles every wave of the first workgroup of every type spends per phase
-#ifndef EQF_W_TRACE
-#define EQF_W_TRACE 0
-#endif
-#if EQF_W_TRACE
-#define WT_STAMP(k)                        \
-  do {                                     \
-    const long long tn = clock64();        \
-    wt[k] += tn - wt_last, wt_last = tn;   \
-  } while (0)
-#else
-#define WT_STAMP(k) \
-  do {              \
-  } while (0)
-#endif
 constexpr int W_WAVES = 4;
 constexpr int W_MAXTYPE = 48;
 constexpr int W_PLANE_FLOATS = 256;  // one bf16 plane of a 16 x 32 tile in fragment order: 64 lanes x 16 bytes
@@ -61,7 +46,7 @@ struct WArgs {
   int x_ld, m_ld, w_ld, E;
   const float *d1, *d2;
   int ld1, ld2;
-  int echunk, ntype, only_type;
+  int echunk, ntype;
   int plane_floats, wave_floats;  // LDS: [2 buffers of planes][per wave: coupling block, four transposition tiles]
   float *db, *db2;
   XGate gate;
@@ -191,24 +176,17 @@ __device__ __forceinline__ void w_wave(const WArgs& g, const WType& T, const WSl
   };
 
   const int nhs = (eend - ebeg + 15) >> 4;
-#if EQF_W_TRACE
-  long long wt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long wt_last = clock64();
-  const long long wt_begin = wt_last;
-#endif
   fetch_b(ebeg);
   fetch_xw(ebeg);
   if constexpr (MPRE) m_fetch<LEN>(mv, g.coupling + S.m_off, g.m_ld, ebeg, eend - 1, lane);
   produce(0, ebeg);
   w_barrier();
-  WT_STAMP(0);  // prologue
 #pragma unroll 1
   for (int hs = 0; hs < nhs; ++hs) {
     const int half = hs & 1, buf = hs & 1;
     const int e_lo = ebeg + 16 * hs;
     const int ec = e_lo + 8 * hi;  // this lane's 8 edges: ec + j
     fetch_b(e_lo + 16);
-    WT_STAMP(6);  // d_out tile requests issued
     if (!half) {  // the coupling block requested one half-step ago (before the loop for the first)
       if constexpr (!MPRE) m_fetch<LEN>(mv, g.coupling + S.m_off, g.m_ld, e_lo, eend - 1, lane);
       wave_lds_order();
@@ -221,7 +199,6 @@ __device__ __forceinline__ void w_wave(const WArgs& g, const WType& T, const WSl
 #pragma unroll
       for (int k = b0; k < b0 + 4 && k < D1 + 1; ++k) tile16_put(Tw + (k & 3) * XT16_FLOATS, k < D1 ? nx[k < D1 ? k : 0] : nw, lane);
       wave_lds_order();
-      if (b0 == 0) WT_STAMP(7);  // x / w tiles arrived and written to LDS
 #pragma unroll
       for (int k = b0; k < b0 + 4 && k < D1 + 1; ++k) {
         float t[8];
@@ -252,7 +229,6 @@ __device__ __forceinline__ void w_wave(const WArgs& g, const WType& T, const WSl
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       if (ec + j >= eend) wq[j] = 0.f;
-    WT_STAMP(1);  // x / w tiles out of the registers, through LDS
     fetch_xw(e_lo + 16);                                                                    // next half-step's x / w
     if constexpr (MPRE)
       if (half) m_fetch<LEN>(mv, g.coupling + S.m_off, g.m_ld, e_lo + 16, eend - 1, lane);  // next block's coupling rows
@@ -289,11 +265,8 @@ __device__ __forceinline__ void w_wave(const WArgs& g, const WType& T, const WSl
         mma_terms<NPA, NPA>(pa, pb, acc[ct]);
       }
     }
-    WT_STAMP(2);  // generation + matrix instructions (issue)
     produce(buf ^ 1, e_lo + 16);
-    WT_STAMP(3);  // own d_out tiles -> planes
     w_barrier();
-    WT_STAMP(4);  // barrier
   }
   // C[row = channel of the slab][column]: register q of lane (r, hi) = row (q & 3) + 8 (q >> 2) + 4 hi, column r
 #pragma unroll
@@ -307,12 +280,6 @@ __device__ __forceinline__ void w_wave(const WArgs& g, const WType& T, const WSl
       atomicAdd(base + (size_t)ch * ldw + r, acc[ct][q]);
     }
   }
-#if EQF_W_TRACE
-  WT_STAMP(5);
-  if (blockIdx.x < 8 * g.ntype && (blockIdx.x & 7) == 0 && lane == 0)
-    printf("wtrace d1 %d d3 %d ct %d wave %d/%d half-steps %d: total %lld prologue %lld issue_b %lld xw_arrive %lld xw_get %lld gen+mma %lld produce %lld barrier %lld epilogue %lld\n",
-           D1, D3, CT, wave, nact, nhs, clock64() - wt_begin, wt[0], wt[6], wt[7], wt[1], wt[2], wt[3], wt[4], wt[5]);
-#endif
   if constexpr (D3 == 1) {
     if (do_bias) {
 #pragma unroll
@@ -332,7 +299,6 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void sfcw_wgrad_kernel(const WArgs
   KERNARG_IN_PLACE(WArgs);
   int chunk, y;
   if (!order_xy(g.ord, blockIdx.x, chunk, y)) return;
-  if (g.only_type >= 0 && y != g.only_type) return;
   const WType T = g.type[y];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (wave >= T.nsl) return;  // (a terminated wave no longer counts at the workgroup's barriers)
@@ -363,12 +329,8 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void sfcw_wgrad_kernel(const WArgs
 #undef W_CASE
 }
 
-#ifndef EQF_W_ROUNDS
-#define EQF_W_ROUNDS 3
-#endif
-static int g_w_rounds = 0;  // development (sfcw_dev_set 0): rounds of resident workgroups the chunk length is sized for
-static int g_w_only = -1;  // development (sfcw_dev_set 2): only the workgroups of this type (index after the cost sort) run
-static int g_w_order = 2;   // development (sfcw_dev_set 1): 0 heaviest-first in batches of 8 chunks per XCD, 1 chunk-major (XCD-aware), 2 type-major, heaviest first
+// rounds of resident workgroups the chunk length is sized for at the bench size (see plan_wgrad2)
+constexpr int W_ROUNDS = 3;
 
 int plan_wgrad2(const SfcCommon& C, const eqf_dtp_paths* P, const XGate* gate, WArgs& A, int& nblk, size_t& lds, int npa) {
   if (!fits32(C) || max_deg(C) > 5) return EQF_E_UNSUPPORTED;
@@ -455,25 +417,20 @@ int plan_wgrad2(const SfcCommon& C, const eqf_dtp_paths* P, const XGate* gate, W
   }
   // (three rounds at the bench size: 152 / 129 / 124 / 133 us for 1 / 2 / 3 / 4; two on graphs of 10-17 k edges: 66 / 60 / 79 us at
   // 10 000, 106 / 89 / 101 at 17 000 -- profiles/r06/r06_ag_*)
-  const int rounds = g_w_rounds > 0 ? g_w_rounds : (C.E >= 22000 ? EQF_W_ROUNDS : 2);
+  const int rounds = C.E >= 22000 ? W_ROUNDS : 2;
   int z = eqf_cdiv(rounds * 512, ntype);
   int echunk = eqf_cdiv(C.E, z);
   echunk = ((echunk + 31) / 32) * 32;
   if (echunk < 64) echunk = 64;
   A.echunk = echunk;
   z = eqf_cdiv(C.E, echunk);
-  if (g_w_order == 1) A.ord = xcd_order(z, ntype, nblk);
-  else A.ord = lpt_order(z, ntype, nblk, g_w_order != 2);
+  // type-major, heaviest type first (measured against heaviest-first in batches of 8 chunks per XCD and chunk-major XCD-aware
+  // orders, both removed; their code is in git history)
+  A.ord = lpt_order(z, ntype, nblk);
   return 0;
 }
 
 }  // namespace
-
-void sfcw_dev_set(int key, int value) {
-  if (key == 0) g_w_rounds = value;
-  if (key == 1) g_w_order = value;
-  if (key == 2) g_w_only = value;
-}
 
 // Text dump of the launch plan for the CPU tests (eqf_sfcx_dev_plan kind 3): header, one line per workgroup type
 int sfcw_dev_plan(const sfc::SfcCommon* Cp, const eqf_dtp_paths* paths, int mode, char* buf, int buflen) {
@@ -515,7 +472,6 @@ int sfcw_wgrad_launch(const sfc::SfcCommon* Cp, const eqf_dtp_paths* paths, int 
   int rc = plan_wgrad2(C, paths, &XG, A, nblk, lds, npa);
   if (rc) return rc;
   A.db = d_bias0, A.db2 = d_bias2;
-  A.only_type = g_w_only;
   hipStream_t st = (hipStream_t)stream;
 #define WG_LAUNCH(M)                                                                                                 \
   do {                                                                                                               \

@@ -125,9 +125,6 @@ __device__ __forceinline__ void tile_sync() {
 // fragment-wise 16-byte LDS reads conflict free and the row-wise writes at most 2-way (tests/test_sfcx_tiles.py).
 constexpr int XT_LD = 36;
 constexpr int XT_FLOATS = 32 * XT_LD;
-#ifndef EQF_XB_TILE_IO
-#define EQF_XB_TILE_IO 1
-#endif
 // issue the four row-major loads of a tile (rows past elast re-read row elast)
 __device__ __forceinline__ void tile_fetch(f32x4 (&t)[4], const float* __restrict__ base, const unsigned ld, const int e0,
                                            const int elast, const int lane) {
@@ -175,9 +172,6 @@ __device__ __forceinline__ void tile_store(float* __restrict__ T, const float (&
 // 8 hi .. 8 hi + 7: two 16-byte-per-lane loads of whole 128-byte lines and a wave-private LDS tile instead of eight 4-byte
 // loads that each touch two lines (weight gradient: both MFMA operands are "lane = column, 8 edges per lane")
 constexpr int XT16_FLOATS = 16 * XT_LD;
-#ifndef EQF_XW_TILE
-#define EQF_XW_TILE 1
-#endif
 struct Tile16 {
   f32x4 t0, t1;
 };
@@ -206,34 +200,6 @@ __device__ __forceinline__ void tile16_get(const float* __restrict__ T, const in
   (void)g_byval
 #else
 #define KERNARG_IN_PLACE(T) const T& g = g_byval
-#endif
-
-// Dev build (-DEQF_XTRACE=1, tools/sfcx_trace.py): serialising clock samples around the two phases of a forward step -- all
-// operands arrived / matrix instructions retired -- for the first workgroups of one XCD.  Not compiled into the product.
-#ifndef EQF_XTRACE
-#define EQF_XTRACE 0
-#endif
-#if EQF_XTRACE
-__device__ __forceinline__ unsigned long long xt_clock() {
-  unsigned long long t;
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define XT_RETIRE(v) asm volatile("v_mov_b32 %0, %0" : "+v"(v))
-// non-serialising sample (only the scalar result is waited for): phase marks of the data-gradient item
-__device__ __forceinline__ unsigned long long xt_mark() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define XT_MARK()                                                    \
-  do {                                                               \
-    if (trace_on && lane == 0 && trace_n < 63) trace_p[++trace_n] = xt_mark(); \
-  } while (0)
-#else
-#define XT_MARK() \
-  do {            \
-  } while (0)
 #endif
 
 template <int N>
@@ -286,9 +252,6 @@ inline int gate_map(const XGate& gt, const eqf_dtp_paths* P, int in_off, int mul
 }
 
 // items sorted by cost (heaviest first) by the planner; see order_xy mode 3
-#ifndef EQF_X_LPT
-#define EQF_X_LPT 1
-#endif
 inline SfcOrder lpt_order(int nx, int ny, int& nblocks, bool batched = false) {
   SfcOrder o;
   o.mode = batched ? 4 : 3, o.nx = nx, o.ny = ny;
@@ -320,7 +283,6 @@ struct XBwdArgs {
   float *dx, *dw, *dM;
   const __bf16* packed;
   int ms;
-  int only_d1;  // development switch: 0, or the only input degree (2 l + 1) whose items run
   int psplit;   // small graphs (L_max <= 2): two waves per item, each runs every other path (sfcx_bwd_kernel)
   XGate gate;
   SfcOrder ord;  // nx = edge tiles, ny = groups of this launch
@@ -329,9 +291,6 @@ struct XBwdArgs {
     long pb;
   } deg[SFC_MAX_DEG];
   XBGroup grp[XB_MAXGRP];
-#if EQF_XTRACE
-  unsigned long long* trace;
-#endif
 };
 
 float* const kDummyF = reinterpret_cast<float*>(16);  // non-null placeholder for tables built without data pointers
@@ -383,9 +342,6 @@ struct XFwdArgs {
     XSeg seg[X_MAXSEG];
   } deg[SFC_MAX_DEG];
   signed char y_deg[16], y_ct0[16], y_ct[16];
-#if EQF_XTRACE
-  unsigned long long* trace;  // dev build: per-step clock samples of the first workgroups (tools/sfcx_trace.py)
-#endif
 };
 
 // column tiles per wave item: 3 / 2 / 1 accumulator tiles per row tile (48 / 96 / 80+ accumulator registers); with 4 tiles
@@ -457,7 +413,7 @@ inline int plan_fwd(const SfcCommon& C, const eqf_dtp_paths* P, int mode, XFwdAr
   // tile, operands from L2) gains 25 % from heaviest-items-first (124 -> 93 us at E = 25 354); the one that streams w [E, 960]
   // (sep_act: 6 items per tile) loses 3 % -- its items no longer meet their tile's x / coupling rows in L2 -- and keeps the
   // tile-major order.
-  if (EQF_X_LPT && C.w == nullptr) {
+  if (C.w == nullptr) {
     // cost of an item = steps x (operand wait + generation + matrix instructions of a step), fitted to the traced steps of
     // profiles/r03/r03_s_what_bounds_the_forward.md
     long cost[16];
@@ -532,7 +488,6 @@ inline int plan_bwd(const SfcCommon& C, const eqf_dtp_paths* P, int mode, XBwdAr
   }
   if (ngrp == 0) return EQF_E_BADARG;
   ngrp_out = ngrp;
-#if EQF_X_LPT
   {  // heaviest groups first (order_xy mode 3): matrix instructions of a group's paths + its register contraction
     long cost[XB_MAXGRP];
     for (int k = 0; k < ngrp; ++k) {
@@ -552,15 +507,10 @@ inline int plan_bwd(const SfcCommon& C, const eqf_dtp_paths* P, int mode, XBwdAr
         cost[b] = cost[b - 1], cost[b - 1] = tc;
       }
   }
-#endif
   if ((C.x_ld | C.w_ld | C.ld1 | C.ld2) & 3) return EQF_E_UNSUPPORTED;  // the row-major tiles are read with 16-byte loads
   A.ms = (msmax + 3) & ~3;  // the transposition tile behind the coupling block stays 16-byte aligned
   lds = (size_t)(32 * A.ms + (1 + 5) * XT_FLOATS) * sizeof(float);  // coupling block + x / w / dx / dw tile + one d_out tile per m3
-#if EQF_X_LPT
   A.ord = lpt_order(eqf_cdiv(C.E, 32), ngrp, nblk, true);
-#else
-  A.ord = xcd_order(eqf_cdiv(C.E, 32), ngrp, nblk);
-#endif
   return 0;
 }
 
@@ -572,5 +522,4 @@ int sfcy_fwd_launch(const sfc::SfcCommon* C, const eqf_dtp_paths* paths, int mod
 // csrc/sfcw.hip: the multi-wave weight gradient (round 6).  EQF_E_UNSUPPORTED: shape outside its tables, nothing launched.
 int sfcw_wgrad_launch(const sfc::SfcCommon* C, const eqf_dtp_paths* paths, int mode, int gate_on, int gS, int gG, float c_silu,
                       float c_sig, float* d_bias0, float* d_bias2, void* stream);
-void sfcw_dev_set(int key, int value);
 int sfcw_dev_plan(const sfc::SfcCommon* C, const eqf_dtp_paths* paths, int mode, char* buf, int buflen);

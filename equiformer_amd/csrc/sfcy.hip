@@ -41,21 +41,6 @@ extern __shared__ __attribute__((aligned(16))) float sy_lds[];
 namespace {
 using namespace sfc;
 
-// development: -DEQF_Y_TRACE=1 prints the cycles one wave of the first workgroup of every item type spends per phase
-#ifndef EQF_Y_TRACE
-#define EQF_Y_TRACE 0
-#endif
-#if EQF_Y_TRACE
-#define YT_STAMP(k)                        \
-  do {                                     \
-    const long long tn = clock64();        \
-    yt[k] += tn - yt_last, yt_last = tn;   \
-  } while (0)
-#else
-#define YT_STAMP(k) \
-  do {              \
-  } while (0)
-#endif
 constexpr int Y_WAVES = 4;
 constexpr int Y_MAXTYPE = 8;
 __host__ __device__ constexpr int y_ctmax(int d3) { return d3 == 1 ? 6 : (d3 == 3 ? 2 : 1); }
@@ -276,16 +261,10 @@ __device__ __forceinline__ void yf_loader(const YFwdArgs& g, const YType& T, con
     }
   }
   int s3 = 0;
-#if EQF_Y_TRACE
-  long long yt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long yt_last = clock64();
-#endif
 #pragma unroll 1
   for (int s = 0; s < nsteps; ++s) {
     wait_vmcnt(n_tail);
-    YT_STAMP(1);  // operands landed
     __builtin_amdgcn_s_barrier();
-    YT_STAMP(2);  // barrier
     const int4* const tq = reinterpret_cast<const int4*>(sy_lds) + 2 * min(s + 3, nsteps - 1);
     const int4 ta = tq[0], tb = tq[1];
     n_tail = 0;
@@ -301,12 +280,7 @@ __device__ __forceinline__ void yf_loader(const YFwdArgs& g, const YType& T, con
     }
     s3 = s3 == 2 ? 0 : s3 + 1;
     E1 = E2, E2 = y_unpack(ta, tb);
-    YT_STAMP(3);  // DMAs issued
   }
-#if EQF_Y_TRACE
-  if (grp == 3 && k == 0 && lane == 0)
-    printf("ytrace loader d3 %d ct %d steps %d: wait %lld barrier %lld issue %lld\n", D.d3, T.ct, nsteps, yt[1], yt[2], yt[3]);
-#endif
 }
 
 // -------------------------------------------------------------------------------------------------------- compute waves
@@ -325,11 +299,6 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
   const int e0 = (grp * Y_WAVES + wave) * 32;  // (tiles past the end run on clamped rows and store nothing)
   const int CT = T.ct, ct0 = T.ct0, nsteps = T.nsteps, E = f.E;
   const bool valid = e0 + r < E;
-#if EQF_Y_TRACE
-  long long yt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long yt_last = clock64();
-  const long long yt_begin = yt_last;
-#endif
   const YMap m = y_map<NPW>(g, T);
   const unsigned wv = m.wv_off + (unsigned)wave * m.wave_bytes;
   float* const Mt = sy_lds + ((wv + m.mb_rel) >> 2);
@@ -356,7 +325,6 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
   YStep E1 = y_entry(sy_lds, min(1, nsteps - 1));
   const bool lead2 = T.nsb == 3;
   int s = 0, s3 = 0;  // s3 = s % 3
-  YT_STAMP(0);
 
   auto run = [&](auto tag, const int nst) __attribute__((always_inline)) {
     constexpr int D1 = decltype(tag)::value;
@@ -372,7 +340,6 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
 #pragma unroll 1
     for (; s < s_end; ++s) {
       __builtin_amdgcn_s_barrier();
-      YT_STAMP(2);  // barrier
       const int4* const tq = reinterpret_cast<const int4*>(sy_lds) + 2 * min(s + 2, nsteps - 1);
       const int4 ta = tq[0], tb = tq[1];
       if (E0.flags & 1) {  // first step of a chunk: its x rows out of their slot
@@ -401,7 +368,6 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
           }
         }
       }
-      YT_STAMP(3);  // x rows out of their slot
       float wf[8];
       if (has_w) {
         const float* const ws = sy_lds + ((wv + m.ws_rel + s3 * 2048) >> 2) + frag0;
@@ -442,7 +408,6 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
           mma_terms<NPA, NPW>(pa, bw, acc[m3][ct]);
         }
       }
-      YT_STAMP(4);  // generation + matrix instructions (issue)
       s3 = s3 == 2 ? 0 : s3 + 1;
       E0 = E1, E1 = y_unpack(ta, tb);
     }
@@ -453,7 +418,6 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
 
   // (two waves per SIMD -- a loader beside a compute wave -- so the register budget is 256 and hipcc keeps the accumulators in
   // VGPRs: no accumulator-file copies.  With 512 registers it copied all of them to VGPRs at the end of every iteration.)
-  YT_STAMP(5);  // accumulators retired
   // epilogue: accumulator register q of lane (r, hi) = row (edge) (q & 3) + 8 (q >> 2) + 4 hi, column r of the tile.  The tile goes
   // through a wave-private LDS image (the wave's x slots are free: the loader's last DMA landed before the last barrier) and
   // leaves as 16-byte stores of whole 128-byte lines, 8 rows per instruction -- 4 store instructions per 32 x 32 tile instead of 16
@@ -490,12 +454,6 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
       }
     }
   }
-#if EQF_Y_TRACE
-  YT_STAMP(6);  // stores issued
-  if (grp == 3 && wave == 0 && lane == 0)
-    printf("ytrace d3 %d ct %d steps %d: total %lld | prologue %lld barrier %lld stage %lld compute %lld retire %lld stores %lld\n",
-           D3, CT, nsteps, clock64() - yt_begin, yt[0], yt[2], yt[3], yt[4], yt[5], yt[6]);
-#endif
 }
 
 template <int MODE>

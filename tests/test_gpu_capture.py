@@ -154,7 +154,7 @@ def test_captured_train_step_with_optimizer_equals_eager_over_two_batches_of_one
         assert abs(a - b) <= 2e-5 * max(1.0, abs(a)), (le, lg)
     # Atomically accumulated weight gradients differ in summation order from launch to launch: the moments agree to
     # that noise; the PARAMETERS agree where the gradient is above it -- Adam's m / (sqrt(v) + eps) turns a noise-level gradient
-    # into a full +-lr step of either sign, in two eager runs as well (tools/capture_debug5.py: 7e-4 after the second eager step).
+    # into a full +-lr step of either sign, in two eager runs as well (measured: 7e-4 after the second eager step).
     assert _rel(mg_, me) < 5e-4, _rel(mg_, me)
     big = me.abs() > 1e-3 * me.abs().max()
     assert int(big.sum()) > 1000

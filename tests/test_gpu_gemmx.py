@@ -129,32 +129,6 @@ def test_accumulate_and_grouped_linear_match_fp32_kernels():
     assert worst < 2e-5
 
 
-def test_one_wave_per_tile_kernels_match_the_tiled_ones():
-    """development variant (eqf_gemmx_dev_set(0, 0)): one wave per 32 x 32 tile, whole K chunks in flight -- same results"""
-    from equiformer_amd import lib as _lib
-    dev = _dev()
-    li, lo = RowLayout("128x0e+64x1e+32x2e"), RowLayout("384x0e+192x1e+96x2e")
-    spec = ops.LinearSpec(li, lo)
-    g = torch.Generator().manual_seed(11)
-    n = 777
-    x, dy = torch.randn(n, li.dim, generator=g).to(dev), torch.randn(n, lo.dim, generator=g).to(dev)
-    w = (torch.randn(spec.weight_numel, generator=g) * 0.1).to(dev)
-    bias = torch.randn(spec.bias_dim, generator=g).to(dev)
-    res = {}
-    for direct in (1, 0):
-        _lib.load().eqf_gemmx_dev_set(0, direct)
-        try:
-            dw, db = torch.zeros_like(w), torch.zeros_like(bias)
-            y, dx = ops._lin_fwd(x, w, bias, spec), ops._lin_dgrad(dy, w, spec)
-            ops._lin_wgrad(x, dy, spec, dw, db)
-            torch.cuda.synchronize()
-            res[direct] = (y, dx, dw, db)
-        finally:
-            _lib.load().eqf_gemmx_dev_set(0, 1)
-    for a, b in zip(res[0], res[1]):
-        assert _rel(a, b) < 2e-6
-
-
 def test_deferred_weight_gradients_equal_immediate_ones():
     """The weight gradients of node-row linears that belong to leaf parameters are queued during a first-order backward and
     launched together when the pass ends (ops._defer_lin_wgrad): same values through .backward() (AccumulateGrad adopts the

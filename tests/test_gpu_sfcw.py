@@ -114,7 +114,7 @@ def test_multi_wave_weight_gradient_against_exact_fp32_kernels(case, mode):
 
 
 def test_gated_bias_variant_and_the_automatic_choice():
-    """eqf_sfcx_bwd_weight_gated_bias through both kernels; variant 0 (automatic) = the multi-wave kernel from EQF_W_MIN_EDGES on."""
+    """eqf_sfcx_bwd_weight_gated_bias through both kernels; variant 0 (automatic) = the multi-wave kernel from W_MIN_EDGES (csrc/sfcx.hip) on."""
     a, _, ab, _ = _wgrad("qm9_sep_value_gated", 25354, 0, 1, bias=True)
     b, _, bb, _ = _wgrad("qm9_sep_value_gated", 25354, 0, 2, bias=True)
     c, _, cb, _ = _wgrad("qm9_sep_value_gated", 25354, 0, 0, bias=True)

@@ -112,7 +112,7 @@ def test_shapes_outside_the_multi_wave_tables_fall_through():
 
 
 def test_multi_wave_forward_is_the_default_at_the_bench_size_and_bit_reproducible():
-    """variant 0 (automatic) = the multi-wave kernel from EQF_Y_MIN_EDGES edges on; six launches give the same bits."""
+    """variant 0 (automatic) = the multi-wave kernel from Y_MIN_EDGES (csrc/sfcx.hip) edges on; six launches give the same bits."""
     a1, a2 = _forward("qm9_sep_act", 25354, 0, 0, seed=3)
     b1, b2 = _forward("qm9_sep_act", 25354, 0, 2, seed=3)
     assert torch.equal(a1, b1) and torch.equal(a2, b2)

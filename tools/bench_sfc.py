@@ -14,7 +14,6 @@ from equiformer_amd.layout import DtpTable, RowLayout  # noqa: E402
 from equiformer_amd.lib import call  # noqa: E402
 
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 25354
-ORDERS = [int(v) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else [-1]
 dev = torch.device("cuda:0")
 P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
 st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -61,30 +60,10 @@ def run(name, irr, sh_irr, out_irr, n2, use_w):
                      P(dx), P(dw), None, E, st())
     wg = lambda: call("eqf_sfc_bwd_weight", P(x), P(M), P(w), table.c_ref, P(d1), lay.c_ref, P(d2), n2, dWl, P(dweight2),
                       E, st())
-    from equiformer_amd import lib as _lib
-    dbg = torch.zeros(8, dtype=torch.int64, device=dev)
-    _lib.load().eqf_sfc_debug_buffer(ctypes.c_void_p(dbg.data_ptr()))
-    f()
-    torch.cuda.synchronize()
-    d = dbg.cpu().tolist()
-    tot = sum(d[:7]) or 1
-    print("%-10s fwd phase share (wave 0): prologue %.2f commit %.2f barrier %.2f issue(B) %.2f mfma %.2f barrier %.2f issue(x,w) %.2f"
-          % ((name,) + tuple(v / tot for v in d[:7])), flush=True)
-    dbg.zero_()
-    b()
-    torch.cuda.synchronize()
-    _lib.load().eqf_sfc_debug_buffer(None)
-    d = dbg.cpu().tolist()
-    nb = ((E + 31) // 32)
-    print("%-10s bwd_data phase cycles per workgroup-row (sum over groups / edge tiles): prologue %.0f staging %.0f mfma %.0f "
-          "epilogue %.0f store %.0f" % ((name,) + tuple(v / nb for v in d[:5])), flush=True)
-    for order in ORDERS:
-        _lib.load().eqf_sfc_debug_order(order)
-        for tag, fn in (("fwd", f), ("bwd_data", b), ("bwd_weight", wg)):
-            us = timeit(fn)
-            print("%-10s order %d %-10s E=%d  %8.1f us  %6.1f TFLOP/s  (%.2f GFLOP)"
-                  % (name, order, tag, E, us, flops / us / 1e6, flops / 1e9), flush=True)
-    _lib.load().eqf_sfc_debug_order(-1)
+    for tag, fn in (("fwd", f), ("bwd_data", b), ("bwd_weight", wg)):
+        us = timeit(fn)
+        print("%-10s %-10s E=%d  %8.1f us  %6.1f TFLOP/s  (%.2f GFLOP)" % (name, tag, E, us, flops / us / 1e6, flops / 1e9),
+              flush=True)
     # split-precision kernels (csrc/sfcx.hip): mode 0 = 2 + 3 planes, 1 = plain bf16, 2 = 3 + 3 planes
     for mode in (0, 1, 2):
         packed = ops._sfc_pack(weight, weight2, spec, mode)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Micro-benchmark of the split-precision SeparableFCTP kernels (csrc/sfcx.hip) at the bench shapes:
-   python tools/bench_sfcx.py [E] [modes, e.g. 0,1] [--l3] [--dm]
+   python tools/bench_sfcx.py [E] [modes, e.g. 0,1] [--l3] [--dm] [--fwd-variant=V] [--wgrad-variant=V] [--no-bwd-split]
 us / call of forward, data gradient, weight gradient.  --l3: the L_max = 3 MD17 shapes as well; --dm: the force-evaluation
 variant (d_coupling) of the data gradient.  A/B of kernel variants: EQF_LIB_VARIANT=<name> (equiformer_amd/build.py --variant)."""
 import ctypes
@@ -21,20 +21,13 @@ dev = torch.device("cuda:0")
 P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
 st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
 L = _lib.load()
-for _a in sys.argv:  # --wgrad-variant=1 (one-wave kernel) / 2 (multi-wave, csrc/sfcw.hip); default 0 = the library's choice
+for _a in sys.argv:  # kernel choice: 0 = the library's, 1 = the one-wave kernel, 2 = the multi-wave kernel (csrc/sfcy.hip, csrc/sfcw.hip)
+    if _a.startswith("--fwd-variant="):
+        L.eqf_sfcx_dev_set(2, int(_a.split("=")[1]))
     if _a.startswith("--wgrad-variant="):
         L.eqf_sfcx_dev_set(4, int(_a.split("=")[1]))
-    if _a.startswith("--bwd-split-slots="):  # wave slots the path-split data gradient may take (0 = never split)
-        v = int(_a.split("=")[1])
-        L.eqf_sfcx_dev_set(9, 1 if v == 0 else 0)
-        if v:
-            L.eqf_sfcx_dev_set(10, v)
-    if _a.startswith("--fwd-split="):  # at most this many waves per forward item on small graphs (1, 2, 4)
-        L.eqf_sfcx_dev_set(11, int(_a.split("=")[1]))
-    if _a.startswith("--wgrad-rounds="):
-        L.eqf_sfcx_dev_set(5, int(_a.split("=")[1]))
-    if _a.startswith("--wgrad-order="):
-        L.eqf_sfcx_dev_set(6, int(_a.split("=")[1]))
+    if _a == "--no-bwd-split":  # the data gradient never splits the paths of an item over two waves
+        L.eqf_sfcx_dev_set(9, 1)
 
 
 def timeit(fn, n=30):
@@ -86,11 +79,6 @@ def run(name, irr, sh_irr, out_irr, n2, use_w, want_dM=False):
         fin = all(torch.isfinite(a).all().item() for a in (dx, dw) if a is not None)
         print("%-10s mode %d%s bwd_data   %7.1f us  (%5.1f TFLOP/s)  finite %s"
               % (name, mode, " dM" if want_dM else "", us, flops / us / 1e6, fin), flush=True)
-        if "--classes" in sys.argv:  # the launch with only the items of one input degree: that class's longest item
-            for dd in (1, 3, 5, 7):
-                L.eqf_sfcx_dev_set(1, dd)
-                print("%-10s            items of d1 = %d only: %7.1f us" % (name, dd, timeit(bw)), flush=True)
-            L.eqf_sfcx_dev_set(1, 0)
         if want_dM:
             continue
         fx = lambda: call("eqf_sfcx_fwd", P(x), P(M), P(w), table.c_ref, PK, None, None, P(o1), lay.c_ref, P(o2), n2, E,  # noqa: E731
@@ -100,17 +88,6 @@ def run(name, irr, sh_irr, out_irr, n2, use_w, want_dM=False):
         for tag, fn in (("fwd", fx), ("bwd_weight", wx)):
             us = timeit(fn)
             print("%-10s mode %d %-10s %7.1f us  (%5.1f TFLOP/s)" % (name, mode, tag, us, flops / us / 1e6), flush=True)
-        if "--wtypes" in sys.argv:  # the multi-wave weight gradient with the workgroups of one type only (index after the cost sort)
-            for ty in range(24):
-                L.eqf_sfcx_dev_set(7, ty)
-                print("%-10s            wgrad workgroups of type %2d only: %7.1f us" % (name, ty, timeit(wx)), flush=True)
-            L.eqf_sfcx_dev_set(7, -1)
-        if "--wclasses" in sys.argv:  # the weight-gradient launch with the items of one (input degree, output degree) class only
-            for di in (1, 3, 5):
-                for do in (1, 3, 5):
-                    L.eqf_sfcx_dev_set(3, 1 + 10 * di + do)
-                    print("%-10s            wgrad items of (d1, d3) = (%d, %d) only: %7.1f us" % (name, di, do, timeit(wx)), flush=True)
-            L.eqf_sfcx_dev_set(3, 0)
 
 
 run("sep_act", "128x0e+64x1e+32x2e", "1x0e+1x1e+1x2e", "224x0e+64x1e+32x2e", 128, True)

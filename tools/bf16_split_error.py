@@ -30,7 +30,7 @@ for K in (224, 384, 672):
     ref = a.double() @ b.double()
     scale = ref.abs().max()
     f32 = (a @ b).double()
-    x3 = gemm_split(a, b, 2, [(0, 0), (0, 1), (1, 0)]).double()
-    x6 = gemm_split(a, b, 3, [(0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1)]).double()
-    print("K=%4d  max|err|/max|ref|:  fp32 %.2e   bf16x3 %.2e   bf16x6 %.2e"
-          % (K, (f32 - ref).abs().max() / scale, (x3 - ref).abs().max() / scale, (x6 - ref).abs().max() / scale))
+    p3 = gemm_split(a, b, 2, [(0, 0), (0, 1), (1, 0)]).double()
+    p6 = gemm_split(a, b, 3, [(0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1)]).double()
+    print("K=%4d  max|err|/max|ref|:  fp32 %.2e   3 products %.2e   6 products %.2e"
+          % (K, (f32 - ref).abs().max() / scale, (p3 - ref).abs().max() / scale, (p6 - ref).abs().max() / scale))

@@ -14,7 +14,6 @@ from equiformer_amd import lib as _lib, ops  # noqa: E402
 from equiformer_amd.layout import RowLayout  # noqa: E402
 
 MODES = sys.argv[1].split(",") if len(sys.argv) > 1 else ["fp32", "split"]
-DIRECT = "--direct" in sys.argv
 dev = torch.device("cuda:0")
 n, E = 2304, 25354
 
@@ -33,11 +32,6 @@ def timeit(fn, k=30):
 
 
 _lib.load()
-if DIRECT:
-    _lib.load().eqf_gemmx_dev_set(0, 0)
-for a in sys.argv:
-    if a.startswith("--tn-minsteps="):
-        _lib.load().eqf_gemmx_dev_set(2, int(a.split("=")[1]))
 rows = []
 CASES = [("node 480 -> 480", "128x0e+64x1e+32x2e", "128x0e+64x1e+32x2e"),
          ("node ffn 480 -> 3x", "128x0e+64x1e+32x2e", "384x0e+192x1e+96x2e"),
