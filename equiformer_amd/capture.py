@@ -8,8 +8,10 @@ host's launch path from the step -- ~0.4 ms of gaps at the head of an eager 10-m
 What stays OUTSIDE the graph, and why:
   * the radius graph (EdgeGraph.from_radius): its edge count is the one data-dependent size of the step and is read back on
     the host.  The captured launches address the index tensors of the graph object the capture ran on; every later step
-    rebuilds the radius graph INTO those tensors (`from_radius(into=...)`).  A step whose node / edge counts differ from the
-    captured ones runs eagerly (and, from `min_eager` eager steps of a shape on, gets a graph of its own: one per shape).
+    rebuilds the radius graph INTO those tensors (`from_radius(into=...)`).  `CapturedTrainStep` keys its graphs on the exact
+    (nodes, edges): a step whose counts differ runs eagerly (and, from `min_eager` eager steps of a shape on, gets a graph of
+    its own).  Batches of a real loader change both counts nearly every step: `BucketedTrainStep` (below) pads each batch to
+    the capacity of a shape bucket with one phantom molecule and keeps one graph per bucket, so almost every step replays.
   * three numbers the captured launches read from device words instead of frozen by-value arguments: the seed offset of
     the attention dropout (a fresh draw per replay: eqf_attn_aggregate_*_dseed) and {lr, 1 - b1^t, sqrt(1 - b2^t)} of AdamW
     (eqf_adamw_step_dev); the host writes them (pinned buffer, asynchronous copy) before it launches the graph.
@@ -40,7 +42,7 @@ class CapturedTrainStep:
         self.opt, self.forward_loss = optimizer, forward_loss
         self.min_eager, self.max_graphs = int(min_eager), int(max_graphs)
         self._graphs = {}   # (N, E) -> dict(graph=CUDAGraph, sg=EdgeGraph, loss=Tensor)
-        self._seen = {}     # (N, E) -> (eager steps so far, last EdgeGraph)
+        self._seen = {}     # (N, E) -> eager steps so far (counts only: an EdgeGraph kept here would never be freed)
         dev = optimizer.flat_p.device
         self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
@@ -79,9 +81,9 @@ class CapturedTrainStep:
         if g is None:
             g = build_graph(None)
         key = (g.N, g.E)
-        n, _ = self._seen.get(key, (0, None))
+        n = self._seen.get(key, 0)
         if n < self.min_eager or len(self._graphs) >= self.max_graphs or not getattr(g, "_radius_static", False):
-            self._seen[key] = (n + 1, g)
+            self._seen[key] = n + 1
             self.eager_steps += 1
             return self._run(g)
         # capture this shape: the launches record the addresses of g's tensors, of the inputs forward_loss reads and of the
@@ -95,6 +97,168 @@ class CapturedTrainStep:
             self.opt._step = step_before  # (capturing enqueued nothing: the step count advances with the replays)
         rec = dict(graph=graph, sg=g, loss=loss)
         self._graphs[key] = rec
+        self._draw_seed()
+        self.opt.advance_captured()
+        graph.replay()
+        self.replays += 1
+        return loss
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Batches whose node / edge counts change from step to step (a real loader): one graph per shape BUCKET, not per exact shape.
+DEFAULT_NODE_STEP = 64     # QM9 bench batch (N = 2 304, E ~ 25 354): (33 reserved + 32 mean round-up) / 2 304 = 2.8 % padded nodes,
+DEFAULT_EDGE_STEP = 1024   # 512 / 25 354 = 2.0 % padded edges on average, 4.0 % at most
+_SEEN_MAX = 4096           # bucket keys the eager-step counter remembers
+
+
+def bucket_of(B, N, E, node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP):
+    """(B, N_cap, E_cap) of a batch of B molecules, N nodes, E edges.  E_cap: E rounded up to a multiple of edge_step, so at most
+    edge_step - 1 phantom edges; N_cap: N plus the phantom nodes that many edges can need (`min_phantom_nodes(edge_step - 1)`,
+    reserved whatever E is, so that the bucket depends on N and E separately), rounded up to a multiple of node_step.  A pure
+    host function of its arguments."""
+    from .graph import min_phantom_nodes
+    node_step, edge_step = int(node_step), int(edge_step)
+    if node_step < 1 or edge_step < 1:
+        raise ValueError("bucket steps must be positive")
+    e_cap = -(-int(E) // edge_step) * edge_step
+    n_cap = -(-(int(N) + min_phantom_nodes(edge_step - 1)) // node_step) * node_step
+    return int(B), n_cap, e_cap
+
+
+def bucket_corner(key, node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP):
+    """The largest real (N, E) that `bucket_of` maps to the bucket `key`."""
+    from .graph import min_phantom_nodes
+    return key[1] - min_phantom_nodes(int(edge_step) - 1), key[2]
+
+
+class PaddedBatch:
+    """What `forward_loss(graph, view)` of a BucketedTrainStep reads: the padded inputs `pos` [N_cap, 3], `z` [N_cap], `batch`
+    [N_cap], the masks `node_mask` [N_cap] / `graph_mask` [B + 1] (1.0 real, 0.0 phantom), `B` (real molecules: constant per
+    bucket, the only count that may be used as a Python number) and every target under its own name, padded with zero rows to
+    B + 1 (per molecule) or N_cap (per node)."""
+
+
+class BucketedTrainStep:
+    """bs = BucketedTrainStep(optimizer, forward_loss, radius, graph_targets=("y",), node_targets=())
+       loss = bs.step(batch)        # batch: mapping with pos [N, 3], z [N], batch [N] (ascending) and the targets; N, E vary
+
+    Every batch is padded to the capacity of its bucket (`bucket_of`) with one phantom molecule (EdgeGraph.from_radius(...,
+    capacity=)), the unchanged kernels run on the padded shape, and one HIP graph per BUCKET replays forward + loss + backward +
+    AdamW.  The phantom molecule shares no edge with a real one; layer norm is per node, softmax per destination, pooling per
+    molecule: real rows are what the unpadded step computes.  forward_loss(graph, view) -> scalar loss must keep the phantom rows
+    out of the loss: reduce per-molecule outputs over `[:view.B]`, per-node outputs with `view.node_mask` -- never with the real
+    node or edge count, which a capture would freeze.  The phantom rows then get a zero upstream gradient and add exact zeros to
+    every parameter gradient.  With drop_path_rate > 0 the padded model draws one more random number per call (B + 1 molecules).
+
+    Records are looked up by the step's own bucket key and live side by side; `max_graphs` is honoured by evicting the least
+    recently used one (its bucket has to be seen `min_eager` times again).  Each record owns its static inputs (the padded graph
+    and target buffers of its bucket), so a batch of another bucket never invalidates a graph.  Eager steps (the first `min_eager`
+    of a bucket) run on the same padded inputs as the replays.  Dropout seed word and AdamW device words as CapturedTrainStep;
+    a reducer and periodic graphs are refused likewise."""
+
+    def __init__(self, optimizer, forward_loss, radius, graph_targets=("y",), node_targets=(), min_eager=3, max_graphs=16,
+                 node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000):
+        if getattr(optimizer, "_reducer", None) is not None:
+            raise ValueError("BucketedTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
+        import collections
+        self.opt, self.forward_loss = optimizer, forward_loss
+        self.radius, self.max_num_neighbors = float(radius), int(max_num_neighbors)
+        self.graph_targets, self.node_targets = tuple(graph_targets), tuple(node_targets)
+        self.min_eager, self.max_graphs = int(min_eager), max(1, int(max_graphs))
+        self.node_step, self.edge_step = int(node_step), int(edge_step)
+        self._graphs = collections.OrderedDict()  # bucket key -> dict(graph, sg, view, loss), least recently used first
+        self._seen = collections.OrderedDict()    # bucket key -> eager steps so far (counts only, at most _SEEN_MAX keys)
+        dev = optimizer.flat_p.device
+        self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self.replays = self.eager_steps = self.captures = self.evictions = 0
+        self.real_edges = self.padded_edges = self.real_nodes = self.padded_nodes = 0
+        self.captures_of = {}  # bucket key -> captures (a key captured twice was evicted in between)
+
+    def live_graphs(self):
+        return list(self._graphs)
+
+    def _run(self, g, view):
+        self.opt.zero_grad(set_to_none=True)
+        loss = self.forward_loss(g, view)
+        loss.backward()
+        self.opt.step()
+        return loss.detach()  # (see CapturedTrainStep._run)
+
+    def _draw_seed(self):
+        self._seed_host[0] = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self._seed_dev.copy_(self._seed_host, non_blocking=True)
+
+    def _view(self, g, B):
+        v = PaddedBatch()
+        # (detached aliases: a model that marks `pos` as requiring grad -- the MD17 force pass -- must not mark the graph's buffer)
+        v.pos, v.z, v.batch = g.pos.detach(), g.z, g.batch
+        v.node_mask, v.graph_mask, v.B = g.node_mask, g.graph_mask, B
+        return v
+
+    def _fill_targets(self, view, batch, g, B, fresh):
+        with torch.no_grad():
+            for names, rows, real in ((self.graph_targets, B + 1, B), (self.node_targets, g.N, g.n_real)):
+                for name in names:
+                    t = batch[name]
+                    if t.shape[0] != real:
+                        raise ValueError("target %r has %d rows, the batch has %d" % (name, t.shape[0], real))
+                    if fresh:
+                        setattr(view, name, torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=g.src.device))
+                    buf = getattr(view, name)
+                    buf[:real].copy_(t, non_blocking=True)
+                    if not fresh:
+                        buf[real:].zero_()
+
+    def step(self, batch):
+        from .graph import EdgeGraph
+        if "cell" in batch:
+            raise ValueError("BucketedTrainStep: radius graphs only (the periodic graph is built eagerly)")
+        b = batch["batch"]
+        B = int(batch["num_graphs"]) if "num_graphs" in batch else int(b[-1].item()) + 1
+        self._draw_seed()  # (the device word goes out BEFORE the graph build's host read-back: it overlaps it)
+        plan = EdgeGraph.radius_plan(batch["pos"], b, self.radius, self.max_num_neighbors, B)
+        key = bucket_of(B, plan.N, plan.E, self.node_step, self.edge_step)
+        self.real_nodes += plan.N
+        self.real_edges += plan.E
+        self.padded_nodes += key[1]
+        self.padded_edges += key[2]
+        rec = self._graphs.get(key)
+        if rec is not None:
+            self._graphs.move_to_end(key)
+            EdgeGraph.from_radius_plan(plan, key[1:], into=rec["sg"], z=batch.get("z"))
+            self._fill_targets(rec["view"], batch, rec["sg"], B, fresh=False)
+            self.opt.advance_captured()
+            rec["graph"].replay()
+            self.replays += 1
+            return rec["loss"]
+        g = EdgeGraph.from_radius_plan(plan, key[1:], z=batch.get("z"))
+        view = self._view(g, B)
+        self._fill_targets(view, batch, g, B, fresh=True)
+        n = self._seen.get(key, 0)
+        if n < self.min_eager:
+            self._seen[key] = n + 1
+            self._seen.move_to_end(key)
+            while len(self._seen) > _SEEN_MAX:
+                self._seen.popitem(last=False)
+            self.eager_steps += 1
+            return self._run(g, view)
+        while len(self._graphs) >= self.max_graphs:  # least recently used out; its bucket earns a graph again
+            old, _ = self._graphs.popitem(last=False)
+            self._seen.pop(old, None)
+            self.evictions += 1
+        # capture this bucket: the launches record the addresses of g's tensors, of the view's buffers and of the gradients /
+        # activations the graph's private pool hands out; they see N_cap, E_cap and B + 1 only
+        self.opt.device_hyper(True)
+        graph = torch.cuda.CUDAGraph()
+        with ops.dropout_seed_offset(self._seed_dev), ops._arena.capture_scope():
+            step_before = self.opt._step
+            with torch.cuda.graph(graph):
+                loss = self._run(g, view)
+            self.opt._step = step_before  # (capturing enqueued nothing: the step count advances with the replays)
+        self._graphs[key] = dict(graph=graph, sg=g, view=view, loss=loss)
+        self.captures += 1
+        self.captures_of[key] = self.captures_of.get(key, 0) + 1
         self._draw_seed()
         self.opt.advance_captured()
         graph.replay()

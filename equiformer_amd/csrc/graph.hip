@@ -1,6 +1,8 @@
 // Graph construction and edge geometry: radius graph -> dst-sorted CSR, edge vectors, spherical harmonics,
 // radial basis.  Molecules are tiny (N ~ 18-80 atoms), so one workgroup owns one molecule and brute-forces its
 // pairs out of L1; the output is already sorted by destination (the order the segmented kernels want).
+#include <algorithm>
+
 #include "common.h"
 #include "geom.h"
 
@@ -245,6 +247,49 @@ __global__ __launch_bounds__(256) void csr_by_source_kernel(const int* __restric
       src_perm[pos] = e;
     }
     __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- padding to a capacity
+// Tail of a batch padded to (n_cap, e_cap) with ONE phantom molecule: P = n_cap - n nodes, Q = e_cap - e edges among them.
+// Phantom node i (0 <= i < P) is the destination of d_i = Q / P + (i < Q % P) edges (in-degrees differ by at most one)
+// whose sources are the d_i nodes that follow it cyclically, (i + 1 .. i + d_i) mod P, written in ascending order: no
+// self-loop and no repeated pair as long as d_i <= P - 1, i.e. Q <= P (P - 1) (checked by the entry point).  Every
+// thread derives its node / edge from its index alone (no scan, no atomics); all stores are bounds-checked.
+constexpr int PAD_LATTICE = 16;      // phantom positions: a 16 x 16 x k lattice ...
+constexpr float PAD_SPACING = 1.5f;  // ... of this spacing (Angstrom): pairwise distinct, every phantom edge vector non-zero
+__global__ __launch_bounds__(256) void graph_pad_tail_kernel(int n, int e, int n_cap, int e_cap, int n_mol,
+                                                             int* __restrict__ row_ptr, int* __restrict__ src,
+                                                             int* __restrict__ dst, int* __restrict__ batch,
+                                                             int* __restrict__ mol_ptr, float* __restrict__ pos,
+                                                             long long* __restrict__ z, float* __restrict__ node_mask,
+                                                             float* __restrict__ graph_mask) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int P = n_cap - n, Q = e_cap - e;
+  const int q = P > 0 ? Q / P : 0, r = P > 0 ? Q - q * P : 0;  // the first r phantom nodes have q + 1 incoming edges
+  if (t == 0) mol_ptr[n_mol + 1] = n_cap;
+  if (graph_mask && t <= n_mol) graph_mask[t] = t < n_mol ? 1.f : 0.f;
+  if (node_mask && t < n_cap) node_mask[t] = t < n ? 1.f : 0.f;
+  if (t < P) {
+    const int node = n + t;
+    row_ptr[node + 1] = e + (t + 1) * q + min(t + 1, r);
+    batch[node] = n_mol;
+    if (pos) {
+      pos[3 * node] = PAD_SPACING * (float)(t % PAD_LATTICE);
+      pos[3 * node + 1] = PAD_SPACING * (float)((t / PAD_LATTICE) % PAD_LATTICE);
+      pos[3 * node + 2] = PAD_SPACING * (float)(t / (PAD_LATTICE * PAD_LATTICE));
+    }
+    if (z) z[node] = 1;
+  }
+  if (t < Q) {
+    int i, k;  // destination (phantom index) and rank inside its row
+    if (t < r * (q + 1)) i = t / (q + 1), k = t - i * (q + 1);
+    else i = r + (t - r * (q + 1)) / q, k = (t - r * (q + 1)) - (i - r) * q;  // (q > 0 here: otherwise Q == r (q + 1))
+    const int d = q + (i < r ? 1 : 0);
+    const int wrapped = max(0, i + d + 1 - P);  // sources that wrapped round to 0 .. wrapped - 1 come first (ascending)
+    const int s = k < wrapped ? k : i + 1 + (k - wrapped);
+    src[e + t] = n + s;
+    dst[e + t] = n + i;
   }
 }
 
@@ -556,6 +601,21 @@ int eqf_csr_by_source(const int* src, const int* row_ptr, const int* mol_ptr, in
   const size_t lds = sizeof(int) * (size_t)(max_mol_nodes > 0 ? max_mol_nodes : 1);
   hipLaunchKernelGGL(csr_by_source_kernel, dim3(n_mol), dim3(256), lds, (hipStream_t)stream, src, row_ptr, mol_ptr, n_mol,
                      src_perm, src_ptr);
+  EQF_CHECK_LAUNCH();
+  return 0;
+}
+
+int eqf_graph_pad_tail(int n, int e, int n_cap, int e_cap, int n_mol, int* row_ptr, int* src, int* dst, int* batch,
+                       int* mol_ptr, float* pos, long long* z, float* node_mask, float* graph_mask, void* stream) {
+  if (!row_ptr || !src || !dst || !batch || !mol_ptr) return EQF_E_BADARG;
+  if (n < 0 || e < 0 || n_mol < 0 || n_cap < n || e_cap < e) return EQF_E_BADARG;
+  const long P = n_cap - n, Q = e_cap - e;
+  if (Q > P * (P - 1)) return EQF_E_BADARG;  // not enough phantom nodes for Q distinct (src, dst) pairs without self-loops
+  if (P > CSR_MAX_NODES) return EQF_E_UNSUPPORTED;  // (the phantom molecule goes through eqf_csr_by_source)
+  const long threads = std::max<long>(std::max<long>(n_cap, Q), (long)n_mol + 1);
+  hipLaunchKernelGGL(graph_pad_tail_kernel, dim3(eqf_cdiv(std::max<long>(threads, 1), 256)), dim3(256), 0,
+                     (hipStream_t)stream, n, e, n_cap, e_cap, n_mol, row_ptr, src, dst, batch, mol_ptr, pos, z, node_mask,
+                     graph_mask);
   EQF_CHECK_LAUNCH();
   return 0;
 }

@@ -36,6 +36,30 @@ def _stream():
 CSR_MAX_NODES = 16384  # nodes per molecule the by-source kernel keeps cursors for (csrc/graph.hip)
 
 
+class GraphDoesNotFit(ValueError):
+    """The real node / edge counts of a batch do not fit the capacity it was to be padded to."""
+
+
+def min_phantom_nodes(q):
+    """Smallest P with P (P - 1) >= q: the phantom nodes that q phantom edges need (distinct ordered pairs, no self-loop)."""
+    q = int(q)
+    if q <= 0:
+        return 0
+    p = int((1.0 + (1.0 + 4.0 * q) ** 0.5) / 2.0)
+    while p * (p - 1) < q:
+        p += 1
+    while p > 1 and (p - 1) * (p - 2) >= q:
+        p -= 1
+    return p
+
+
+class RadiusPlan:
+    """The first half of a radius graph build: per-node degrees, their scan and the host read-back of the edge count.  A caller
+    that picks the capacity FROM the counts (equiformer_amd/capture.py: the bucket of a batch) runs the two halves itself:
+    `plan = EdgeGraph.radius_plan(...)`, then `EdgeGraph.from_radius_plan(plan, capacity, into)`."""
+    __slots__ = ("pos", "b32", "N", "E", "num_graphs", "mol_ptr", "row_ptr", "max_mol_nodes", "r", "max_num_neighbors")
+
+
 class EdgeGraph:
     """N nodes, E directed edges sorted by dst.  All index tensors are int32 on the GPU."""
 
@@ -70,10 +94,16 @@ class EdgeGraph:
         self.mol_ptr = _ptr_from_counts(torch.bincount(batch.to(torch.int64), minlength=self.num_graphs))
 
     @staticmethod
-    def from_radius(pos, batch, r, max_num_neighbors=1000, num_graphs=None, into=None):
+    def from_radius(pos, batch, r, max_num_neighbors=1000, num_graphs=None, into=None, capacity=None, z=None):
         """Radius graph per molecule (nodes of a molecule contiguous, `batch` ascending).  into: a graph of an earlier call; when
         this call finds the same node and edge counts its index tensors are REWRITTEN in place and `into` is returned -- the
-        launches of a HIP-graph-captured step (equiformer_amd/capture.py) read those addresses."""
+        launches of a HIP-graph-captured step (equiformer_amd/capture.py) read those addresses.
+
+        capacity=(N_cap, E_cap): the batch is padded to that shape with one phantom molecule (`from_radius_plan`); `into` is then
+        a padded graph of the same capacity.  Raises GraphDoesNotFit, with `into` untouched, when the counts do not fit."""
+        if capacity is not None:
+            plan = EdgeGraph.radius_plan(pos, batch, r, max_num_neighbors, num_graphs)
+            return EdgeGraph.from_radius_plan(plan, capacity, into=into, z=z)
         if not pos.is_cuda:
             raise ops.HipOnlyError("radius graph construction runs on the GPU only")
         pos = pos.detach().to(torch.float32).contiguous()
@@ -116,6 +146,82 @@ class EdgeGraph:
         g.batch = b32
         g.num_graphs = int(num_graphs)
         g.mol_ptr = mol_ptr
+        return g
+
+    # ---- radius graph padded to a capacity (one phantom molecule: csrc/graph.hip eqf_graph_pad_tail) ------------------------
+    @staticmethod
+    def radius_plan(pos, batch, r, max_num_neighbors=1000, num_graphs=None):
+        """Degrees + scan + the one host read-back of a radius graph build; nothing of an earlier graph is touched."""
+        if not pos.is_cuda:
+            raise ops.HipOnlyError("radius graph construction runs on the GPU only")
+        p = RadiusPlan()
+        p.pos = pos.detach().to(torch.float32).contiguous()
+        p.N = int(p.pos.shape[0])
+        p.num_graphs = int(batch[-1].item()) + 1 if num_graphs is None else int(num_graphs)
+        p.r, p.max_num_neighbors = float(r), int(max_num_neighbors)
+        dev = p.pos.device
+        p.b32 = _i32(batch)
+        st = _stream()
+        stats = torch.empty(2, dtype=torch.int32, device=dev)  # [E, nodes of the largest molecule]
+        p.mol_ptr = torch.empty(p.num_graphs + 2, dtype=torch.int32, device=dev)  # (+ 1 entry: the phantom molecule's end)
+        call("eqf_segment_ptr", _P(p.b32), p.N, p.num_graphs, _P(p.mol_ptr), _P(stats, 4), st)
+        deg = torch.empty(p.N, dtype=torch.int32, device=dev)
+        call("eqf_radius_graph_count", _P(p.pos), _P(p.mol_ptr), p.num_graphs, p.r, p.max_num_neighbors, _P(deg), st)
+        p.row_ptr = torch.empty(p.N + 1, dtype=torch.int32, device=dev)
+        call("eqf_exclusive_scan_i32", _P(deg), p.N, _P(p.row_ptr), _P(stats), st)
+        p.E, p.max_mol_nodes = stats.tolist()  # the one host sync of graph construction
+        return p
+
+    @staticmethod
+    def from_radius_plan(plan, capacity, into=None, z=None):
+        """Second half: the graph of `plan` padded to capacity = (N_cap, E_cap).  The result presents N = N_cap nodes, E = E_cap
+        edges and num_graphs = B + 1 molecules to the kernels; the last molecule is a phantom that owns the tail nodes and edges
+        and shares no edge with a real one.  The graph OWNS the padded per-node inputs the model is then called with: `pos`
+        [N_cap, 3], `batch` [N_cap], `z` [N_cap] (int64; only when z is given), and the float masks `node_mask` [N_cap],
+        `graph_mask` [B + 1] (1 real, 0 phantom); `n_real`, `e_real`, `num_real_graphs` hold the real counts (host integers:
+        never use them inside a captured step).  into: a padded graph of the same capacity and molecule count, refilled in
+        place and returned.  Raises GraphDoesNotFit before anything of `into` is written."""
+        n_cap, e_cap = int(capacity[0]), int(capacity[1])
+        N, E, B = plan.N, plan.E, plan.num_graphs
+        P, Q = n_cap - N, e_cap - E
+        if Q < 0 or P < min_phantom_nodes(Q):
+            raise GraphDoesNotFit("%d nodes / %d edges do not fit the capacity (%d, %d): %d phantom edges need %d phantom nodes"
+                                  % (N, E, n_cap, e_cap, max(Q, 0), min_phantom_nodes(max(Q, 0))))
+        if max(plan.max_mol_nodes, P) > CSR_MAX_NODES:
+            raise ops.HipOnlyError("padded radius graphs need molecules (the phantom one included) of at most %d nodes" % CSR_MAX_NODES)
+        dev = plan.pos.device
+        st = _stream()
+        reuse = (into is not None and getattr(into, "_padded", False) and into.N == n_cap and into.E == e_cap
+                 and into.num_graphs == B + 1 and into.src.device == dev and (into.z is None) == (z is None))
+        if reuse:
+            g = into
+        else:
+            g = EdgeGraph.__new__(EdgeGraph)
+            i32 = dict(dtype=torch.int32, device=dev)
+            g.N, g.E, g.num_graphs = n_cap, e_cap, B + 1
+            g.src, g.dst = torch.empty(e_cap, **i32), torch.empty(e_cap, **i32)
+            g.row_ptr, g.batch, g.mol_ptr = torch.empty(n_cap + 1, **i32), torch.empty(n_cap, **i32), torch.empty(B + 2, **i32)
+            g.src_perm, g.src_ptr = torch.empty(e_cap, **i32), torch.empty(n_cap + 1, **i32)
+            g.pos = torch.empty((n_cap, 3), dtype=torch.float32, device=dev)
+            g.z = torch.empty(n_cap, dtype=torch.int64, device=dev) if z is not None else None
+            g.node_mask = torch.empty(n_cap, dtype=torch.float32, device=dev)
+            g.graph_mask = torch.empty(B + 1, dtype=torch.float32, device=dev)
+            g._padded = g._radius_static = True
+            g.capacity = (n_cap, e_cap)
+        g.n_real, g.e_real, g.num_real_graphs = N, E, B
+        with torch.no_grad():
+            g.row_ptr[:N + 1].copy_(plan.row_ptr)
+            g.mol_ptr[:B + 1].copy_(plan.mol_ptr[:B + 1])
+            g.batch[:N].copy_(plan.b32)
+            g.pos[:N].copy_(plan.pos)
+            if z is not None:
+                g.z[:N].copy_(z)
+        call("eqf_radius_graph_fill", _P(plan.pos), _P(plan.mol_ptr), B, plan.r, plan.max_num_neighbors, _P(plan.row_ptr),
+             _P(g.src), _P(g.dst), st)
+        call("eqf_graph_pad_tail", N, E, n_cap, e_cap, B, _P(g.row_ptr), _P(g.src), _P(g.dst), _P(g.batch), _P(g.mol_ptr),
+             _P(g.pos), _P(g.z), _P(g.node_mask), _P(g.graph_mask), st)
+        call("eqf_csr_by_source", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
+             _P(g.src_perm), _P(g.src_ptr), st)
         return g
 
     @staticmethod

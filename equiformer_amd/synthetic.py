@@ -47,3 +47,22 @@ def md17_aspirin_batch(num_frames, jitter=0.05, seed=0):
     return dict(pos=torch.from_numpy(pos.astype(np.float32)), z=torch.from_numpy(z.astype(np.int64)),
                 batch=torch.from_numpy(batch.astype(np.int64)), y=torch.from_numpy(rng.standard_normal(num_frames).astype(np.float32)),
                 dy=torch.from_numpy(rng.standard_normal((num_frames * n, 3)).astype(np.float32)))
+
+
+def qm9_like_varying_batches(num_batches, num_molecules, atoms_range=(12, 24), side=6.5, min_dist=0.9, seed=0):
+    """What a real loader yields: `num_batches` batches of `num_molecules` molecules whose atom counts are drawn uniformly from
+    atoms_range (inclusive) -- different sizes inside a batch, different node / edge totals between batches.  A list of dicts
+    like `qm9_like_batch`'s, plus num_graphs (int) and natoms [B] i64."""
+    rng = np.random.default_rng(seed)
+    lo, hi = int(atoms_range[0]), int(atoms_range[1])
+    out = []
+    for _ in range(num_batches):
+        natoms = rng.integers(lo, hi + 1, size=num_molecules)
+        pos = np.concatenate([_sample_points(rng, int(n), side, min_dist) for n in natoms])
+        z = rng.choice(QM9_Z, size=int(natoms.sum()), p=QM9_P)
+        batch = np.repeat(np.arange(num_molecules), natoms)
+        y = rng.standard_normal(num_molecules)
+        out.append(dict(pos=torch.from_numpy(pos.astype(np.float32)), z=torch.from_numpy(z.astype(np.int64)),
+                        batch=torch.from_numpy(batch.astype(np.int64)), y=torch.from_numpy(y.astype(np.float32)),
+                        num_graphs=int(num_molecules), natoms=torch.from_numpy(natoms.astype(np.int64))))
+    return out

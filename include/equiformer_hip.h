@@ -109,6 +109,23 @@ int eqf_exclusive_scan_i32(const int* counts, int n, int* ptr, int* total, void*
 int eqf_csr_by_source(const int* src, const int* row_ptr, const int* mol_ptr, int n_mol, int max_mol_nodes,
                       int* src_perm, int* src_ptr, void* stream);
 
+/* Pads a collated batch of n nodes / e dst-sorted edges / n_mol molecules to the capacity (n_cap, e_cap) its tensors
+ * were allocated at, with ONE phantom molecule (index n_mol) that owns the P = n_cap - n tail nodes and the
+ * Q = e_cap - e tail edges: a batch of any size then presents the shape of its bucket to the kernels (and to a
+ * captured HIP graph) while no edge joins a phantom node to a real one.  [stands beside the reference's collation and
+ * radius graph -- torch_geometric DataLoader, main_qm9.py:204-216; radius_graph,
+ * nets/graph_attention_transformer.py:866-867 -- which emit the exact, step-dependent sizes.]
+ * One launch, no allocation, no host synchronisation; writes only
+ *   row_ptr[n+1 .. n_cap], src / dst[e .. e_cap): phantom node i receives Q / P (+ 1 for i < Q % P) edges from the
+ *     nodes that follow it cyclically, ascending inside the row: dst-sorted, src != dst, no repeated pair;
+ *   batch[n .. n_cap) = n_mol, mol_ptr[n_mol + 1] = n_cap (mol_ptr has n_mol + 2 entries);
+ *   pos[n .. n_cap) (may be NULL): pairwise distinct lattice points fixed by the phantom index;
+ *   z[n .. n_cap) = 1 (64-bit atomic numbers, may be NULL);
+ *   node_mask[n_cap], graph_mask[n_mol + 1] (may be NULL): 1.0 for real rows, 0.0 for phantom ones.
+ * Needs Q <= P (P - 1) (else EQF_E_BADARG) and P <= 16384 (eqf_csr_by_source's limit, else EQF_E_UNSUPPORTED). */
+int eqf_graph_pad_tail(int n, int e, int n_cap, int e_cap, int n_mol, int* row_ptr, int* src, int* dst, int* batch,
+                       int* mol_ptr, float* pos, long long* z, float* node_mask, float* graph_mask, void* stream);
+
 /* edge_vec = pos[src] - pos[dst] (+ offsets, may be NULL), len = |edge_vec|,
  * sh = Y^0..Y^lmax(edge_vec/len) * sqrt(2l+1)  ("component" normalisation), lmax <= 3.
  * [ref: nets/graph_attention_transformer.py:868-870,874;  e3nn o3.spherical_harmonics] */
