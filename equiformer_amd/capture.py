@@ -6,9 +6,11 @@ host's launch path from the step -- ~0.4 ms of gaps at the head of an eager 10-m
 [ref: the train loop, engine.py:58-92; SURVEY.md 8d "HIP-graph captured where possible"]
 
 What stays OUTSIDE the graph, and why:
-  * the radius graph (EdgeGraph.from_radius): its edge count is the one data-dependent size of the step and is read back on
+  * the radius graph (EdgeGraph.from_radius; periodic structures: EdgeGraph.from_radius_pbc): its edge count is the one data-dependent size of the step and is read back on
     the host.  The captured launches address the index tensors of the graph object the capture ran on; every later step
-    rebuilds the radius graph INTO those tensors (`from_radius(into=...)`).  `CapturedTrainStep` keys its graphs on the exact
+    rebuilds the radius graph INTO those tensors (`from_radius(into=...)`, `from_radius_pbc(into=...)`: the graph's flag
+    `_radius_static` says "every tensor of it is refilled in place by enqueue-only kernels", whichever builder made it -- the
+    by-source view of the periodic graph comes from eqf_csr_by_source_multi, not from a device sort).  `CapturedTrainStep` keys its graphs on the exact
     (nodes, edges): a step whose counts differ runs eagerly (and, from `min_eager` eager steps of a shape on, gets a graph of
     its own).  Batches of a real loader change both counts nearly every step: `BucketedTrainStep` (below) pads each batch to
     the capacity of a shape bucket with one phantom molecule and keeps one graph per bucket, so almost every step replays.
@@ -17,12 +19,15 @@ What stays OUTSIDE the graph, and why:
     (eqf_adamw_step_dev); the host writes them (pinned buffer, asynchronous copy) before it launches the graph.
 
 The MD17 force-loss step (forces by a create_graph backward inside the forward, then a second-order backward) is captured the
-same way (tests/test_gpu_capture.py; bench.py --workload md17_l2: 463 -> 619 frames/s, md17_l3: 218 -> 254).
+same way (tests/test_gpu_capture.py; bench.py --workload md17_l2: 463 -> 619 frames/s, md17_l3: 218 -> 254).  The OC20 step on
+periodic structures (`model(data, graph=g, offsets=g.offsets)`) is captured exact-shape and bucketed alike
+(tests/test_gpu_periodic_capture.py, tools/bench_varying_oc20.py).
 
 Limits: one process / one GPU (a data-parallel reducer's collectives stay eager: `CapturedTrainStep` refuses a reducer),
-attention dropout together with a create_graph backward (no model of the reference combines them), radius graphs only (the
-periodic OC20 graph builds its by-source view with a device sort: eager), inputs other than the graph at fixed addresses
-(`forward_loss` reads the same tensors every step; copy a new batch into them)."""
+attention dropout together with a create_graph backward (no model of the reference combines them), graphs built on the GPU from
+positions only (an edge list that comes from outside -- OC20 with otf_graph=False -- is sorted by EdgeGraph.from_edges with a
+device sort on the host side of the step: eager), inputs other than the graph at fixed addresses (`forward_loss` reads the same
+tensors every step; copy a new batch into them)."""
 import torch
 
 from . import ops
@@ -33,7 +38,9 @@ class CapturedTrainStep:
        loss = cs.step(build_graph)          # every train step
 
     forward_loss(graph) -> scalar loss, reading the batch from tensors that keep their addresses; build_graph(into) -> the
-    EdgeGraph of this step's batch (`EdgeGraph.from_radius(pos, batch, r, into=into)`), called OUTSIDE the capture.
+    EdgeGraph of this step's batch (`EdgeGraph.from_radius(pos, batch, r, into=into)`, or for periodic structures
+    `EdgeGraph.from_radius_pbc(pos, cell, batch, r, k, into=into)[0]`, whose `.offsets` forward_loss passes on), called OUTSIDE
+    the capture.
     optimizer: a FlatAdamW without a reducer."""
 
     def __init__(self, optimizer, forward_loss, min_eager=3, max_graphs=4):
@@ -135,12 +142,19 @@ class PaddedBatch:
     """What `forward_loss(graph, view)` of a BucketedTrainStep reads: the padded inputs `pos` [N_cap, 3], `z` [N_cap], `batch`
     [N_cap], the masks `node_mask` [N_cap] / `graph_mask` [B + 1] (1.0 real, 0.0 phantom), `B` (real molecules: constant per
     bucket, the only count that may be used as a Python number) and every target under its own name, padded with zero rows to
-    B + 1 (per molecule) or N_cap (per node)."""
+    B + 1 (per molecule) or N_cap (per node).  Periodic batches: also `offsets` [E_cap, 3] / `cell_offsets` [E_cap, 3] (zero rows
+    for phantom edges) and `atomic_numbers` (= `z`), so that the view itself is the `data` of the OC20 model:
+    `model(view, graph=graph, offsets=view.offsets)` with "tags" among the node targets."""
 
 
 class BucketedTrainStep:
     """bs = BucketedTrainStep(optimizer, forward_loss, radius, graph_targets=("y",), node_targets=())
        loss = bs.step(batch)        # batch: mapping with pos [N, 3], z [N], batch [N] (ascending) and the targets; N, E vary
+
+    A batch with `cell` [B, 3, 3] is periodic: the graph is the periodic one (EdgeGraph.radius_pbc_plan / from_radius_pbc_plan,
+    `radius` and `max_num_neighbors` of the constructor), `atomic_numbers` is accepted for `z`, and per-node INPUTS such as the
+    OC20 `tags` travel through `node_targets` (a zero row is a valid tag).  One instance serves periodic or non-periodic
+    batches, not both.
 
     Every batch is padded to the capacity of its bucket (`bucket_of`) with one phantom molecule (EdgeGraph.from_radius(...,
     capacity=)), the unchanged kernels run on the padded shape, and one HIP graph per BUCKET replays forward + loss + backward +
@@ -154,7 +168,7 @@ class BucketedTrainStep:
     recently used one (its bucket has to be seen `min_eager` times again).  Each record owns its static inputs (the padded graph
     and target buffers of its bucket), so a batch of another bucket never invalidates a graph.  Eager steps (the first `min_eager`
     of a bucket) run on the same padded inputs as the replays.  Dropout seed word and AdamW device words as CapturedTrainStep;
-    a reducer and periodic graphs are refused likewise."""
+    a reducer is refused likewise."""
 
     def __init__(self, optimizer, forward_loss, radius, graph_targets=("y",), node_targets=(), min_eager=3, max_graphs=16,
                  node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000):
@@ -174,6 +188,7 @@ class BucketedTrainStep:
         self.replays = self.eager_steps = self.captures = self.evictions = 0
         self.real_edges = self.padded_edges = self.real_nodes = self.padded_nodes = 0
         self.captures_of = {}  # bucket key -> captures (a key captured twice was evicted in between)
+        self._periodic = None  # set by the first batch
 
     def live_graphs(self):
         return list(self._graphs)
@@ -194,6 +209,8 @@ class BucketedTrainStep:
         # (detached aliases: a model that marks `pos` as requiring grad -- the MD17 force pass -- must not mark the graph's buffer)
         v.pos, v.z, v.batch = g.pos.detach(), g.z, g.batch
         v.node_mask, v.graph_mask, v.B = g.node_mask, g.graph_mask, B
+        if getattr(g, "_pbc", False):
+            v.offsets, v.cell_offsets, v.atomic_numbers = g.offsets, g.cell_offsets, g.z
         return v
 
     def _fill_targets(self, view, batch, g, B, fresh):
@@ -212,12 +229,21 @@ class BucketedTrainStep:
 
     def step(self, batch):
         from .graph import EdgeGraph
-        if "cell" in batch:
-            raise ValueError("BucketedTrainStep: radius graphs only (the periodic graph is built eagerly)")
+        periodic = "cell" in batch
+        if self._periodic is None:
+            self._periodic = periodic
+        elif self._periodic != periodic:
+            raise ValueError("BucketedTrainStep: one instance serves periodic or non-periodic batches, not both")
         b = batch["batch"]
         B = int(batch["num_graphs"]) if "num_graphs" in batch else int(b[-1].item()) + 1
+        z = batch["z"] if "z" in batch else batch.get("atomic_numbers")
         self._draw_seed()  # (the device word goes out BEFORE the graph build's host read-back: it overlaps it)
-        plan = EdgeGraph.radius_plan(batch["pos"], b, self.radius, self.max_num_neighbors, B)
+        if periodic:
+            plan = EdgeGraph.radius_pbc_plan(batch["pos"], batch["cell"], b, self.radius, self.max_num_neighbors, B)
+            build = EdgeGraph.from_radius_pbc_plan
+        else:
+            plan = EdgeGraph.radius_plan(batch["pos"], b, self.radius, self.max_num_neighbors, B)
+            build = EdgeGraph.from_radius_plan
         key = bucket_of(B, plan.N, plan.E, self.node_step, self.edge_step)
         self.real_nodes += plan.N
         self.real_edges += plan.E
@@ -226,13 +252,13 @@ class BucketedTrainStep:
         rec = self._graphs.get(key)
         if rec is not None:
             self._graphs.move_to_end(key)
-            EdgeGraph.from_radius_plan(plan, key[1:], into=rec["sg"], z=batch.get("z"))
+            build(plan, key[1:], into=rec["sg"], z=z)
             self._fill_targets(rec["view"], batch, rec["sg"], B, fresh=False)
             self.opt.advance_captured()
             rec["graph"].replay()
             self.replays += 1
             return rec["loss"]
-        g = EdgeGraph.from_radius_plan(plan, key[1:], z=batch.get("z"))
+        g = build(plan, key[1:], z=z)
         view = self._view(g, B)
         self._fill_targets(view, batch, g, B, fresh=True)
         n = self._seen.get(key, 0)

@@ -250,6 +250,70 @@ __global__ __launch_bounds__(256) void csr_by_source_kernel(const int* __restric
   }
 }
 
+// The same view for rows that may hold a source SEVERAL times (a periodic row holds it once per image), equal sources
+// not necessarily adjacent.  Inside a row the stable order of equal sources is the edge order, so the slot of edge e is
+// cur[src] + (edges before e in its row with the same source); the cursors advance only after the whole row was
+// placed (LDS atomics, one per edge), so no thread reads a cursor that another one is bumping.  Rows are short
+// (max_neighbors), the quadratic scan of a row reads addresses the whole wave shares.  lds_nodes = the cursors the
+// launch reserved: a molecule with more nodes is skipped (the entry point has refused it already).
+__global__ __launch_bounds__(256) void csr_by_source_multi_kernel(const int* __restrict__ src, const int* __restrict__ row_ptr,
+                                                                  const int* __restrict__ mol_ptr, int n_mol, int lds_nodes,
+                                                                  int* __restrict__ src_perm, int* __restrict__ src_ptr) {
+  extern __shared__ int cur[];  // [nm]
+  __shared__ int part[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int n0 = mol_ptr[b], n1 = mol_ptr[b + 1], nm = n1 - n0;
+  if (nm < 0 || nm > lds_nodes) return;
+  const int e0 = row_ptr[n0], e1 = row_ptr[n1];
+  for (int i = t; i < nm; i += 256) cur[i] = 0;
+  __syncthreads();
+  for (int e = e0 + t; e < e1; e += 256) {
+    const int sn = src[e] - n0;
+    if ((unsigned)sn < (unsigned)nm) atomicAdd(&cur[sn], 1);
+  }
+  __syncthreads();
+  // exclusive scan of cur[0..nm) in place
+  const int chunk = (nm + 255) / 256;
+  const int i0 = min(nm, t * chunk), i1 = min(nm, i0 + chunk);
+  int s = 0;
+  for (int i = i0; i < i1; ++i) s += cur[i];
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const int v = (t >= o) ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int run = e0 + part[t] - s;
+  for (int i = i0; i < i1; ++i) {
+    const int c = cur[i];
+    cur[i] = run;
+    src_ptr[n0 + i] = run;
+    run += c;
+  }
+  if (b == n_mol - 1 && t == 0) src_ptr[n1] = e1;
+  __syncthreads();
+  for (int d = n0; d < n1; ++d) {
+    const int r0 = row_ptr[d], r1 = row_ptr[d + 1];
+    for (int e = r0 + t; e < r1; e += 256) {
+      const int se = src[e], sn = se - n0;
+      int k = 0;
+      for (int q = r0; q < e; ++q) k += (src[q] == se) ? 1 : 0;
+      if ((unsigned)sn < (unsigned)nm) {
+        const int pos = cur[sn] + k;
+        if (pos >= e0 && pos < e1) src_perm[pos] = e;
+      }
+    }
+    __syncthreads();
+    for (int e = r0 + t; e < r1; e += 256) {
+      const int sn = src[e] - n0;
+      if ((unsigned)sn < (unsigned)nm) atomicAdd(&cur[sn], 1);
+    }
+    __syncthreads();
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- padding to a capacity
 // Tail of a batch padded to (n_cap, e_cap) with ONE phantom molecule: P = n_cap - n nodes, Q = e_cap - e edges among them.
 // Phantom node i (0 <= i < P) is the destination of d_i = Q / P + (i < Q % P) edges (in-degrees differ by at most one)
@@ -601,6 +665,27 @@ int eqf_csr_by_source(const int* src, const int* row_ptr, const int* mol_ptr, in
   const size_t lds = sizeof(int) * (size_t)(max_mol_nodes > 0 ? max_mol_nodes : 1);
   hipLaunchKernelGGL(csr_by_source_kernel, dim3(n_mol), dim3(256), lds, (hipStream_t)stream, src, row_ptr, mol_ptr, n_mol,
                      src_perm, src_ptr);
+  EQF_CHECK_LAUNCH();
+  return 0;
+}
+
+int eqf_csr_by_source_multi(const int* src, const int* row_ptr, const int* mol_ptr, int n_mol, int max_mol_nodes,
+                            int* src_perm, int* src_ptr, void* stream) {
+  if (!row_ptr || !mol_ptr || !src_perm || !src_ptr || !src) return EQF_E_BADARG;
+  if (max_mol_nodes > CSR_MAX_NODES) return EQF_E_UNSUPPORTED;
+  if (n_mol <= 0) return 0;
+  static bool attr_done[64] = {};  // per device (function attribute)
+  int dev_id = 0;
+  (void)hipGetDevice(&dev_id);
+  bool& attr = attr_done[dev_id & 63];
+  if (!attr) {
+    hipFuncSetAttribute((const void*)csr_by_source_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        CSR_MAX_NODES * (int)sizeof(int));
+    attr = true;
+  }
+  const int lds_nodes = max_mol_nodes > 0 ? max_mol_nodes : 1;
+  hipLaunchKernelGGL(csr_by_source_multi_kernel, dim3(n_mol), dim3(256), sizeof(int) * (size_t)lds_nodes, (hipStream_t)stream,
+                     src, row_ptr, mol_ptr, n_mol, lds_nodes, src_perm, src_ptr);
   EQF_CHECK_LAUNCH();
   return 0;
 }

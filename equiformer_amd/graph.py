@@ -60,6 +60,13 @@ class RadiusPlan:
     __slots__ = ("pos", "b32", "N", "E", "num_graphs", "mol_ptr", "row_ptr", "max_mol_nodes", "r", "max_num_neighbors")
 
 
+class PbcPlan:
+    """The first half of a periodic graph build (`EdgeGraph.radius_pbc_plan`): RadiusPlan's fields plus the cells, the candidate
+    scan of the nearest-k selection and the candidate total (the size of its scratch)."""
+    __slots__ = ("pos", "cell", "b32", "N", "E", "C", "num_graphs", "mol_ptr", "row_ptr", "cand_ptr", "max_mol_nodes", "r",
+                 "max_num_neighbors")
+
+
 class EdgeGraph:
     """N nodes, E directed edges sorted by dst.  All index tensors are int32 on the GPU."""
 
@@ -78,7 +85,7 @@ class EdgeGraph:
             call("eqf_csr_by_source", _P(src), _P(row_ptr), _P(mol_ptr), int(mol_ptr.shape[0]) - 1, int(max_mol_nodes),
                  _P(self.src_perm), _P(self.src_ptr), _stream())
         else:
-            # arbitrary edge lists (periodic images can repeat a source inside a row): stable device sort
+            # arbitrary edge lists (they may repeat a source inside a row and need not be structure-blocked): stable device sort
             order = torch.argsort(src.to(torch.int64), stable=True)
             self.src_perm = _i32(order)
             self.src_ptr = _ptr_from_counts(torch.bincount(src.to(torch.int64), minlength=self.N))
@@ -224,45 +231,157 @@ class EdgeGraph:
              _P(g.src_perm), _P(g.src_ptr), st)
         return g
 
+    # ---- periodic radius graph (csrc/graph.hip pbc_count / pbc_fill; by-source view: eqf_csr_by_source_multi) ------------------
     @staticmethod
-    def from_radius_pbc(pos, cell, batch, r, max_num_neighbors=50, num_graphs=None):
-        """Periodic radius graph (ocpmodels radius_graph_pbc + get_pbc_distances semantics, see csrc/graph.hip).
-        Returns (graph, offsets[E,3] Cartesian, cell_offsets[E,3] int32); edges are dst-sorted."""
+    def radius_pbc_plan(pos, cell, batch, r, max_num_neighbors=50, num_graphs=None):
+        """Candidate counts, degrees, their scans and the one host read-back of a periodic graph build; nothing of an earlier
+        graph is touched (`radius_plan` for the periodic search)."""
         if not pos.is_cuda:
             raise ops.HipOnlyError("radius graph construction runs on the GPU only")
-        pos = pos.detach().to(torch.float32).contiguous()
-        cell = cell.detach().to(torch.float32).contiguous().view(-1, 3, 3)
-        N = pos.shape[0]
-        if num_graphs is None:
-            num_graphs = int(cell.shape[0])
-        dev = pos.device
-        b32 = _i32(batch)
+        p = PbcPlan()
+        p.pos = pos.detach().to(torch.float32).contiguous()
+        p.cell = cell.detach().to(torch.float32).contiguous().view(-1, 3, 3)
+        p.N = int(p.pos.shape[0])
+        p.num_graphs = int(p.cell.shape[0]) if num_graphs is None else int(num_graphs)
+        p.r, p.max_num_neighbors = float(r), int(max_num_neighbors)
+        dev = p.pos.device
+        p.b32 = _i32(batch)
         st = _stream()
         stats = torch.empty(3, dtype=torch.int32, device=dev)  # [E, nodes of the largest structure, candidates]
-        mol_ptr = torch.empty(num_graphs + 1, dtype=torch.int32, device=dev)
-        call("eqf_segment_ptr", _P(b32), N, int(num_graphs), _P(mol_ptr), _P(stats, 4), st)
-        cand = torch.empty(N, dtype=torch.int32, device=dev)
-        deg = torch.empty(N, dtype=torch.int32, device=dev)
-        call("eqf_radius_graph_pbc_count", _P(pos), _P(cell), _P(mol_ptr), num_graphs, float(r), int(max_num_neighbors),
+        p.mol_ptr = torch.empty(p.num_graphs + 2, dtype=torch.int32, device=dev)  # (+ 1 entry: a phantom structure's end)
+        call("eqf_segment_ptr", _P(p.b32), p.N, p.num_graphs, _P(p.mol_ptr), _P(stats, 4), st)
+        cand = torch.empty(p.N, dtype=torch.int32, device=dev)
+        deg = torch.empty(p.N, dtype=torch.int32, device=dev)
+        call("eqf_radius_graph_pbc_count", _P(p.pos), _P(p.cell), _P(p.mol_ptr), p.num_graphs, p.r, p.max_num_neighbors,
              _P(cand), _P(deg), st)
-        row_ptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        cand_ptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        call("eqf_exclusive_scan_i32", _P(deg), N, _P(row_ptr), _P(stats), st)
-        call("eqf_exclusive_scan_i32", _P(cand), N, _P(cand_ptr), _P(stats, 8), st)
-        E, _, C = stats.tolist()  # the one host sync
+        p.row_ptr = torch.empty(p.N + 1, dtype=torch.int32, device=dev)
+        p.cand_ptr = torch.empty(p.N + 1, dtype=torch.int32, device=dev)
+        call("eqf_exclusive_scan_i32", _P(deg), p.N, _P(p.row_ptr), _P(stats), st)
+        call("eqf_exclusive_scan_i32", _P(cand), p.N, _P(p.cand_ptr), _P(stats, 8), st)
+        p.E, p.max_mol_nodes, p.C = stats.tolist()  # the one host sync
+        return p
+
+    @staticmethod
+    def _pbc_fill(plan, src, dst, cell_offsets, offsets):
+        """The E real edges of `plan` into the head of the given tensors (row_ptr of the plan: real rows only)."""
+        scratch = torch.empty(max(plan.C, 1), dtype=torch.float32, device=plan.pos.device)
+        call("eqf_radius_graph_pbc_fill", _P(plan.pos), _P(plan.cell), _P(plan.mol_ptr), plan.num_graphs, plan.r,
+             plan.max_num_neighbors, _P(plan.row_ptr), _P(plan.cand_ptr), _P(scratch), _P(src), _P(dst), _P(cell_offsets),
+             _P(offsets), _stream())
+
+    @staticmethod
+    def from_radius_pbc(pos, cell, batch, r, max_num_neighbors=50, num_graphs=None, into=None, capacity=None, z=None):
+        """Periodic radius graph (ocpmodels radius_graph_pbc + get_pbc_distances semantics, see csrc/graph.hip).
+        Returns (graph, offsets[E,3] Cartesian, cell_offsets[E,3] int32); edges are dst-sorted.  The graph keeps both per-edge
+        tensors as `graph.offsets` / `graph.cell_offsets`.
+
+        into: a periodic graph of an earlier call; when this call finds the same node, structure and edge counts every index
+        tensor, `offsets` and `cell_offsets` are REWRITTEN in place and `into` is returned (what a captured step reads,
+        equiformer_amd/capture.py); with other counts the result is a fresh graph and `into` is marked as abandoned.
+        capacity=(N_cap, E_cap): the batch is padded to that shape with one phantom structure (`from_radius_pbc_plan`); raises
+        GraphDoesNotFit, with `into` untouched, when the counts do not fit."""
+        plan = EdgeGraph.radius_pbc_plan(pos, cell, batch, r, max_num_neighbors, num_graphs)
+        if capacity is not None:
+            g = EdgeGraph.from_radius_pbc_plan(plan, capacity, into=into, z=z)
+            return g, g.offsets, g.cell_offsets
+        N, E, B = plan.N, plan.E, plan.num_graphs
+        dev = plan.pos.device
+        mol_ptr = plan.mol_ptr[:B + 1]
+        cand = (into is not None and getattr(into, "_pbc", False) and not getattr(into, "_padded", False)
+                and getattr(into, "_radius_static", False))
+        if cand and (into.N, into.E, into.num_graphs, into.src.device) == (N, E, B, dev):
+            with torch.no_grad():
+                into.row_ptr.copy_(plan.row_ptr)
+                into.mol_ptr.copy_(mol_ptr)
+                if into.batch.data_ptr() != plan.b32.data_ptr():
+                    into.batch.copy_(plan.b32)
+            EdgeGraph._pbc_fill(plan, into.src, into.dst, into.cell_offsets, into.offsets)
+            call("eqf_csr_by_source_multi", _P(into.src), _P(into.row_ptr), _P(into.mol_ptr), B, int(plan.max_mol_nodes),
+                 _P(into.src_perm), _P(into.src_ptr), _stream())
+            return into, into.offsets, into.cell_offsets
+        if cand:
+            into._radius_static = False  # (abandoned: its owner falls back to an eager step on the fresh graph)
         src = torch.empty(E, dtype=torch.int32, device=dev)
         dst = torch.empty(E, dtype=torch.int32, device=dev)
         cell_offsets = torch.empty((E, 3), dtype=torch.int32, device=dev)
         offsets = torch.empty((E, 3), dtype=torch.float32, device=dev)
-        scratch = torch.empty(max(C, 1), dtype=torch.float32, device=dev)
-        call("eqf_radius_graph_pbc_fill", _P(pos), _P(cell), _P(mol_ptr), num_graphs, float(r), int(max_num_neighbors),
-             _P(row_ptr), _P(cand_ptr), _P(scratch), _P(src), _P(dst), _P(cell_offsets), _P(offsets), st)
-        # a source can occur several times in a row (different images): generic by-source path
-        g = EdgeGraph(N, src, dst, row_ptr)
-        g.batch = b32
-        g.num_graphs = int(num_graphs)
+        EdgeGraph._pbc_fill(plan, src, dst, cell_offsets, offsets)
+        if plan.max_mol_nodes <= CSR_MAX_NODES:
+            # a source occurs once per image in a row: the cursor kernel that ranks equal sources inside the row, no device sort
+            g = EdgeGraph.__new__(EdgeGraph)
+            g.N, g.E = N, E
+            g.src, g.dst, g.row_ptr = src, dst, plan.row_ptr
+            g.src_perm = torch.empty(E, dtype=torch.int32, device=dev)
+            g.src_ptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+            call("eqf_csr_by_source_multi", _P(src), _P(plan.row_ptr), _P(mol_ptr), B, int(plan.max_mol_nodes),
+                 _P(g.src_perm), _P(g.src_ptr), _stream())
+            g._radius_static = True  # (refillable in place: every tensor comes from an enqueue-only kernel)
+        else:
+            g = EdgeGraph(N, src, dst, plan.row_ptr)  # (structures beyond the cursor kernel's LDS: stable device sort)
+            g._radius_static = False
+        g._pbc = True
+        g.batch = plan.b32
+        g.num_graphs = B
         g.mol_ptr = mol_ptr
+        g.offsets, g.cell_offsets = offsets, cell_offsets
         return g, offsets, cell_offsets
+
+    @staticmethod
+    def from_radius_pbc_plan(plan, capacity, into=None, z=None):
+        """Second half: the periodic graph of `plan` padded to capacity = (N_cap, E_cap) with one phantom structure
+        (eqf_graph_pad_tail), as `from_radius_plan` pads the radius graph: N = N_cap, E = E_cap, num_graphs = B + 1, the padded
+        inputs `pos`, `batch`, `z`, the masks `node_mask` / `graph_mask` and the host integers `n_real`, `e_real`,
+        `num_real_graphs` have the same meaning.  In addition the graph owns `offsets` [E_cap, 3] and `cell_offsets` [E_cap, 3];
+        phantom edges get zero rows in both (the phantom nodes sit on pairwise distinct lattice points: no zero-length edge).
+        into: a padded periodic graph of the same capacity and structure count, refilled in place and returned.  Raises
+        GraphDoesNotFit before anything of `into` is written."""
+        n_cap, e_cap = int(capacity[0]), int(capacity[1])
+        N, E, B = plan.N, plan.E, plan.num_graphs
+        P, Q = n_cap - N, e_cap - E
+        if P < 0 or Q < 0 or P < min_phantom_nodes(Q):
+            raise GraphDoesNotFit("%d nodes / %d edges do not fit the capacity (%d, %d): %d phantom edges need %d phantom nodes"
+                                  % (N, E, n_cap, e_cap, max(Q, 0), min_phantom_nodes(max(Q, 0))))
+        if max(plan.max_mol_nodes, P) > CSR_MAX_NODES:
+            raise ops.HipOnlyError("padded periodic graphs need structures (the phantom one included) of at most %d nodes"
+                                   % CSR_MAX_NODES)
+        dev = plan.pos.device
+        st = _stream()
+        reuse = (into is not None and getattr(into, "_padded", False) and getattr(into, "_pbc", False) and into.N == n_cap
+                 and into.E == e_cap and into.num_graphs == B + 1 and into.src.device == dev and (into.z is None) == (z is None))
+        if reuse:
+            g = into
+        else:
+            g = EdgeGraph.__new__(EdgeGraph)
+            i32 = dict(dtype=torch.int32, device=dev)
+            g.N, g.E, g.num_graphs = n_cap, e_cap, B + 1
+            g.src, g.dst = torch.empty(e_cap, **i32), torch.empty(e_cap, **i32)
+            g.row_ptr, g.batch, g.mol_ptr = torch.empty(n_cap + 1, **i32), torch.empty(n_cap, **i32), torch.empty(B + 2, **i32)
+            g.src_perm, g.src_ptr = torch.empty(e_cap, **i32), torch.empty(n_cap + 1, **i32)
+            g.cell_offsets = torch.empty((e_cap, 3), **i32)
+            g.offsets = torch.empty((e_cap, 3), dtype=torch.float32, device=dev)
+            g.pos = torch.empty((n_cap, 3), dtype=torch.float32, device=dev)
+            g.z = torch.empty(n_cap, dtype=torch.int64, device=dev) if z is not None else None
+            g.node_mask = torch.empty(n_cap, dtype=torch.float32, device=dev)
+            g.graph_mask = torch.empty(B + 1, dtype=torch.float32, device=dev)
+            g._padded = g._radius_static = g._pbc = True
+            g.capacity = (n_cap, e_cap)
+        g.n_real, g.e_real, g.num_real_graphs = N, E, B
+        with torch.no_grad():
+            g.row_ptr[:N + 1].copy_(plan.row_ptr)
+            g.mol_ptr[:B + 1].copy_(plan.mol_ptr[:B + 1])
+            g.batch[:N].copy_(plan.b32)
+            g.pos[:N].copy_(plan.pos)
+            if z is not None:
+                g.z[:N].copy_(z)
+            if Q:
+                g.offsets[E:].zero_()
+                g.cell_offsets[E:].zero_()
+        EdgeGraph._pbc_fill(plan, g.src, g.dst, g.cell_offsets, g.offsets)
+        call("eqf_graph_pad_tail", N, E, n_cap, e_cap, B, _P(g.row_ptr), _P(g.src), _P(g.dst), _P(g.batch), _P(g.mol_ptr),
+             _P(g.pos), _P(g.z), _P(g.node_mask), _P(g.graph_mask), st)
+        call("eqf_csr_by_source_multi", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
+             _P(g.src_perm), _P(g.src_ptr), st)
+        return g
 
     @staticmethod
     def from_edges(edge_src, edge_dst, N, batch=None, num_graphs=None):

@@ -131,10 +131,17 @@ class GraphAttentionTransformerOC20(_Trunk):
         graph, order = EdgeGraph.from_edges(edge_index[0], edge_index[1], pos.shape[0], batch)
         return graph, offsets[order].contiguous()
 
-    def forward(self, data):
+    def forward(self, data, graph=None, offsets=None):
+        """graph: an EdgeGraph built by the caller (EdgeGraph.from_radius_pbc, also with into= / capacity=) together with its
+        Cartesian `offsets` (default: graph.offsets); `_graph` is then not called -- no neighbour search and no host read-back
+        inside the forward, which is what a captured step needs (equiformer_amd/capture.py).  A padded graph has one phantom
+        structure: the energies come back as [B + 1, 1] and the caller slices them."""
         pos = data.pos.to(torch.float32).contiguous()
         batch = data.batch
-        graph, offsets = self._graph(data, pos, batch)
+        if graph is None:
+            graph, offsets = self._graph(data, pos, batch)
+        elif offsets is None:
+            offsets = getattr(graph, "offsets", None)
         atom_embedding, _, _ = self.atom_embed(data.atomic_numbers.long())
         tag_embedding, _, _ = self.tag_embed(data.tags.long())
         node_features, ectx = self._trunk_features(atom_embedding + tag_embedding, pos, graph, offsets)

@@ -66,3 +66,27 @@ def qm9_like_varying_batches(num_batches, num_molecules, atoms_range=(12, 24), s
                         batch=torch.from_numpy(batch.astype(np.int64)), y=torch.from_numpy(y.astype(np.float32)),
                         num_graphs=int(num_molecules), natoms=torch.from_numpy(natoms.astype(np.int64))))
     return out
+
+
+def oc20_like_varying_batches(num_batches, num_structures, atoms_range=(60, 96), cell=(11.0, 11.0, 30.0), seed=0):
+    """What an OC20 loader yields: `num_batches` batches of `num_structures` slab-shaped periodic structures (orthorhombic cell
+    with the given edge lengths in Angstrom, atoms uniform in its lower 45 %: slab + adsorbate below vacuum, SURVEY.md section
+    8(d)) whose atom counts are drawn uniformly from atoms_range (inclusive).  A list of dicts: pos [N, 3] f32, atomic_numbers
+    [N] i64 (1..83), tags [N] i64 (0..2), batch [N] i64 ascending, cell [B, 3, 3] f32, natoms [B] i64, num_graphs (int),
+    y [B] f32 (energy targets)."""
+    rng = np.random.default_rng(seed)
+    lo, hi = int(atoms_range[0]), int(atoms_range[1])
+    edge = np.asarray(cell, dtype=np.float64).reshape(3)
+    out = []
+    for _ in range(num_batches):
+        natoms = rng.integers(lo, hi + 1, size=num_structures)
+        n = int(natoms.sum())
+        pos = rng.uniform(0.0, 1.0, size=(n, 3)) * np.array([1.0, 1.0, 0.45]) * edge
+        cells = np.tile(np.diag(edge)[None], (num_structures, 1, 1))
+        out.append(dict(pos=torch.from_numpy(pos.astype(np.float32)),
+                        atomic_numbers=torch.from_numpy(rng.integers(1, 84, size=n).astype(np.int64)),
+                        tags=torch.from_numpy(rng.integers(0, 3, size=n).astype(np.int64)),
+                        batch=torch.from_numpy(np.repeat(np.arange(num_structures), natoms).astype(np.int64)),
+                        cell=torch.from_numpy(cells.astype(np.float32)), natoms=torch.from_numpy(natoms.astype(np.int64)),
+                        num_graphs=int(num_structures), y=torch.from_numpy(rng.standard_normal(num_structures).astype(np.float32))))
+    return out

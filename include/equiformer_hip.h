@@ -103,11 +103,18 @@ int eqf_radius_graph_pbc_fill(const float* pos, const float* cell, const int* mo
  * eqf_exclusive_scan_i32: ptr[0..n] = exclusive prefix sums of counts[n]; total (may be NULL) receives ptr[n].
  * eqf_csr_by_source: for a dst-sorted edge list whose edges never cross the molecules of mol_ptr and whose rows
  *   hold every source at most once: src_perm[E] = stable argsort of src, src_ptr[N+1] = offsets of the by-source
- *   groups.  max_mol_nodes = an upper bound of the nodes per molecule (<= 16384, else EQF_E_UNSUPPORTED).          */
+ *   groups.  max_mol_nodes = an upper bound of the nodes per molecule (<= 16384, else EQF_E_UNSUPPORTED).
+ * eqf_csr_by_source_multi: the same outputs (element for element the stable argsort of src and the scan of its
+ *   counts) for rows that may hold a source any number of times, adjacent or not: the periodic graph, where a
+ *   neighbour occurs once per image.  Replaces the by-source grouping that `scatter` over `edge_src` needs
+ *   [ref: nets/graph_attention_transformer_oc20.py:267-302] without a device sort: enqueue-only, legal between two
+ *   replays of a captured step and inside a capture.                                                              */
 int eqf_segment_ptr(const int* seg_of, int n, int n_seg, int* ptr, int* max_len, void* stream);
 int eqf_exclusive_scan_i32(const int* counts, int n, int* ptr, int* total, void* stream);
 int eqf_csr_by_source(const int* src, const int* row_ptr, const int* mol_ptr, int n_mol, int max_mol_nodes,
                       int* src_perm, int* src_ptr, void* stream);
+int eqf_csr_by_source_multi(const int* src, const int* row_ptr, const int* mol_ptr, int n_mol, int max_mol_nodes,
+                            int* src_perm, int* src_ptr, void* stream);
 
 /* Pads a collated batch of n nodes / e dst-sorted edges / n_mol molecules to the capacity (n_cap, e_cap) its tensors
  * were allocated at, with ONE phantom molecule (index n_mol) that owns the P = n_cap - n tail nodes and the
