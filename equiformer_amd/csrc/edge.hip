@@ -257,14 +257,17 @@ __global__ __launch_bounds__(256) void alpha_bwd_kernel(const float* __restrict_
   const int h = col / Kh, H = HK / Kh;
   const int e0 = blockIdx.y * CH, e1 = min(E, e0 + CH);
   const float ad = adot[col];
-  float acc = 0.f;
+  // d_alpha_dot[col] is a sum of signed terms over all edges that often nearly cancels: the CH products of a thread are formed
+  // and added in fp64 (16 adds per thread) and rounded once, so what the column loses is the rounding of its terms and of the
+  // E / CH atomics, not a serial fp32 chain
+  double acc = 0.0;
   for (int e = e0; e < e1; ++e) {
     const float g = d_logit[(long)e * H + h] * c;
     const float av = a[(long)e * HK + col];
     da[(long)e * HK + col] = g * ad * dslrelu(av);
-    acc += g * slrelu(av);
+    acc += (double)g * (double)slrelu(av);
   }
-  atomicAdd(d_adot + col, acc);
+  atomicAdd(d_adot + col, (float)acc);
 }
 
 // float4 columns, RP edge rows per pass, four passes in flight: the column-per-thread kernel above walks 16 edges in a

@@ -16,13 +16,15 @@ struct SegTab {
   int l[EQF_MAX_SEG];
   int woff[EQF_MAX_SEG];  // offset into affine_weight
   int boff[EQF_MAX_SEG];  // offset into affine_bias (l == 0 only, else -1)
+  int zidx[EQF_MAX_SEG];  // index among the 0e segments (column of the saved means), 0 for the others
+  int n0;                 // 0e segments per row, at least 1: the saved means are [rows][n0]
   int D;
 };
 
 SegTab make_segtab(const eqf_irreps& ir) {
   SegTab t{};
   t.nseg = ir.nseg;
-  int off = 0, w = 0, b = 0;
+  int off = 0, w = 0, b = 0, n0 = 0;
   for (int s = 0; s < ir.nseg; ++s) {
     t.off[s] = off;
     t.mul[s] = ir.mul[s];
@@ -33,11 +35,13 @@ SegTab make_segtab(const eqf_irreps& ir) {
     t.len[s] = ir.mul[s] * (2 * ir.l[s] + 1);
     t.woff[s] = w;
     t.boff[s] = scalar ? b : -1;
+    t.zidx[s] = scalar ? n0++ : 0;
     w += ir.mul[s];
     if (scalar) b += ir.mul[s];
     off += t.len[s];
   }
   t.D = off;
+  t.n0 = n0 > 0 ? n0 : 1;
   return t;
 }
 
@@ -57,7 +61,6 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
   const float* x2r = x2 ? x2 + (long)row * T.D : nullptr;
   float* sr = x2 ? xsum + (long)row * T.D : nullptr;
   float* yr = y + (long)row * T.D;
-  bool first0 = true;
   for (int s = 0; s < T.nseg; ++s) {
     const int off = T.off[s];
     const int n = T.len[s], mul = T.mul[s];
@@ -75,9 +78,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     const float rs = rsqrtf(wave_sum(sq) / n + eps);
     if (lane == 0) {
       rstd[(long)row * T.nseg + s] = rs;
-      if (T.l[s] == 0 && first0) mean0[row] = mean;
+      if (T.l[s] == 0) mean0[(long)row * T.n0 + T.zidx[s]] = mean;
     }
-    if (T.l[s] == 0) first0 = false;
     const float* ws = w + T.woff[s];
     for (int i = lane; i < n; i += 64) {
       const int u = i % mul;
@@ -155,6 +157,7 @@ __global__ __launch_bounds__(256) void layernorm_wgrad_kernel(const float* __res
   while (s + 1 < T.nseg && c >= T.off[s + 1]) ++s;
   const int u = (c - T.off[s]) % T.mul[s];
   const bool is0 = T.l[s] == 0;
+  const int n0 = T.n0, z = T.zidx[s];
   // LN_WGRAD_ROWS rows per thread in chunks of CH: the CH rows of a chunk are requested before the first is used
   // (compile-time trip count, rows past the end clamped and masked).  The cost of this kernel is its atomics (same-address
   // fp32 atomics retire at ~0.35 ns each): 64 rows per thread = 37 k of them at 2 304 rows instead of 147 k with 16.
@@ -167,7 +170,7 @@ __global__ __launch_bounds__(256) void layernorm_wgrad_kernel(const float* __res
       gv[k] = dy[(long)r * T.D + c];
       xs[k] = x[(long)r * T.D + c];
       rs[k] = rstd[(long)r * T.nseg + s];
-      m0[k] = is0 ? mean0[r] : 0.f;  // mean0 holds the mean of the first 0e segment; other 0e segments (none in practice) recompute
+      m0[k] = is0 ? mean0[(long)r * n0 + z] : 0.f;  // the forward saved one mean per (row, 0e segment): [rows][n0]
     }
 #pragma unroll
     for (int k = 0; k < CH; ++k) {

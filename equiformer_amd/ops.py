@@ -227,6 +227,16 @@ def _zeros2(n1, n2, device):
 
 
 # ------------------------------------------------------------------------------------------------- layer norm
+def _ln_means(layout):
+    """Columns of the saved channel means: one per 0e segment of the row (include/equiformer_hip.h: mean0 is
+    [rows, max(1, number of 0e segments)])."""
+    n = getattr(layout, "_ln_means", None)
+    if n is None:
+        c = layout.c
+        n = layout._ln_means = max(1, sum(1 for s in range(c.nseg) if c.l[s] == 0 and not c.odd[s]))
+    return n
+
+
 class _LayerNorm(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, layout, eps):
@@ -235,7 +245,7 @@ class _LayerNorm(Function):
         n = x.shape[0]
         y = torch.empty_like(x)
         rstd = torch.empty((n, len(layout.segs)), device=x.device, dtype=torch.float32)
-        mean0 = torch.empty((n,), device=x.device, dtype=torch.float32)
+        mean0 = torch.empty((n, _ln_means(layout)), device=x.device, dtype=torch.float32)
         call("eqf_layernorm_fwd", _p(x), _p(weight), _p(bias), _p(y), _p(rstd), _p(mean0), n, layout.c_ref,
              float(eps), _stream())
         ctx.save_for_backward(x, weight, rstd, mean0, bias)
@@ -310,7 +320,7 @@ class _AddLayerNorm(Function):
         s = torch.empty_like(a)
         y = torch.empty_like(a)
         rstd = torch.empty((n, len(layout.segs)), device=a.device, dtype=torch.float32)
-        mean0 = torch.empty((n,), device=a.device, dtype=torch.float32)
+        mean0 = torch.empty((n, _ln_means(layout)), device=a.device, dtype=torch.float32)
         call("eqf_add_layernorm_fwd", _p(a), _p(b), _p(s), _p(weight), _p(bias), _p(y), _p(rstd), _p(mean0), n,
              layout.c_ref, float(eps), _stream())
         ctx.save_for_backward(s, weight, rstd, mean0)

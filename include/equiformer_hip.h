@@ -357,8 +357,9 @@ int eqf_sfcx_bwd_weight_gated_bias(const float* x_raw, const eqf_gate_in* gate, 
  * Row-local feature ops (nodes or edges)
  * ------------------------------------------------------------------------------------------- */
 
-/* EquivariantLayerNormV2 ('component' normalisation, affine).  rstd is [rows, nseg], mean0 is [rows]
- * (mean of the first 0e segment); both are outputs of fwd and inputs of bwd.
+/* EquivariantLayerNormV2 ('component' normalisation, affine).  rstd is [rows, nseg], mean0 is
+ * [rows, max(1, number of 0e segments)]: the channel mean of every 0e segment in row order ([rows] for the usual row
+ * with one 0e segment); both are outputs of fwd and inputs of bwd.
  * [ref: nets/layer_norm.py:89-152] */
 int eqf_layernorm_fwd(const float* x, const float* weight, const float* bias, float* y, float* rstd,
                       float* mean0, int rows, const eqf_irreps* irreps, float eps, void* stream);

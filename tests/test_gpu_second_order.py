@@ -183,6 +183,25 @@ def test_attn_aggregate_bwd2(head_irr, H):
              [logit, value], [0, 1], 15)
 
 
+@pytest.mark.parametrize("head_irr,H", [("32x0e+16x1e+8x2e", 4), ("32x0e+16x1e+16x2e+8x3e", 4)])
+def test_attn_aggregate_bwd2_ragged(head_irr, H):
+    """eqf_attn_aggregate_bwd2 on ragged rows: in-degrees 0..9, 62..69 and 127..130 with empty rows first and last, for the
+    heads of 30 float4 groups (half-wave first-order kernels) and 54 (full kernels)"""
+    from types import SimpleNamespace
+    from equiformer_amd import ops
+    from equiformer_amd.irreps import Irreps
+    from equiformer_amd.layout import RowLayout
+    import fp64_ops as fo
+    graph = fo.ragged_graph(fo.ATTN_DEGREES, 9, 30, device=_dev())
+    lay = RowLayout(" + ".join("%dx%de" % (mul * H, ir.l) for mul, ir in Irreps(head_irr)))
+    g = torch.Generator().manual_seed(31)
+    logit = (torch.randn(graph.E, H, generator=g, dtype=torch.float64) * 2.0).requires_grad_(True)
+    value = torch.randn(graph.E, lay.dim, generator=g, dtype=torch.float64).requires_grad_(True)
+    gcpu = SimpleNamespace(dst=graph.dst.cpu(), N=graph.N)
+    _compare(lambda lo, va: ops.attn_aggregate(lo, va, graph, H, lay), lambda lo, va: so.attn_aggregate(lo, va, gcpu, H, lay),
+             [logit, value], [0, 1], 32)
+
+
 def test_attn_aggregate_bwd2_with_dropout_is_consistent():
     """With alpha_drop > 0 there is no restatement to compare with (the mask is a hash of the seed); the second-order
     kernel must agree with finite differences of the first-order backward under the SAME seed."""
