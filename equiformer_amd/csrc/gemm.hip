@@ -689,7 +689,7 @@ extern "C" {
 
 int eqf_gemm_nn(const float* A, eqf_rows ra, const float* B, int ldb, float* C, eqf_rows rc, const float* bias, int M,
                 int N, int K, int accumulate, void* stream) {
-  if (!A || !B || !C || ra.d < 1 || rc.d < 1) return EQF_E_BADARG;
+  if (!A || !B || !C || ra.d < 1 || rc.d < 1 || K < 1) return EQF_E_BADARG;  // K: a feature width, never empty
   RowsArgs a{};
   a.A = {A, ra.d, ra.ld, ra.inner};
   a.B = {B, 1, ldb, 0};
@@ -703,7 +703,7 @@ int eqf_gemm_nn(const float* A, eqf_rows ra, const float* B, int ldb, float* C, 
 
 int eqf_gemm_nt(const float* A, eqf_rows ra, const float* B, int ldb, float* C, eqf_rows rc, const float* bias, int M,
                 int N, int K, int accumulate, void* stream) {
-  if (!A || !B || !C || ra.d < 1 || rc.d < 1) return EQF_E_BADARG;
+  if (!A || !B || !C || ra.d < 1 || rc.d < 1 || K < 1) return EQF_E_BADARG;  // K: a feature width, never empty
   RowsArgs a{};
   a.A = {A, ra.d, ra.ld, ra.inner};
   a.B = {B, 1, ldb, 0};
@@ -737,6 +737,13 @@ int eqf_gemm_tn_colsum(const float* A, eqf_rows ra, const float* B, eqf_rows rb,
 int eqf_gemm_group(const eqf_gemm_desc* d, int n, void* stream) {
   if (!d || n < 1 || n > MAX_GROUP) return EQF_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
+  // every descriptor is checked before the first launch (as eqf_gemmx_group: same contract); kinds 0, 1: K is a feature width,
+  // never empty -- an empty batch is M <= 0, or K <= 0 for the weight gradients
+  for (int i = 0; i < n; ++i) {
+    if (d[i].kind < 0 || d[i].kind > 3) return EQF_E_BADARG;
+    if (!d[i].A || !d[i].B || !d[i].C || d[i].ra.d < 1 || d[i].rc.d < 1) return EQF_E_BADARG;
+    if (d[i].kind < 2 && d[i].K < 1) return EQF_E_BADARG;
+  }
   // rows problems (kind 0: C = A B, kind 1: C = A B^T) share one launch per kind; tn problems (kind 2) another
   for (int kind = 0; kind < 2; ++kind) {
     RowsGroup G{};

@@ -560,6 +560,9 @@ int eqf_gemmx_group(const eqf_gemm_desc* d, int n, int mode, void* stream) {
   for (int i = 0; i < n; ++i) {
     if (d[i].kind < 0 || d[i].kind > 3) return EQF_E_BADARG;
     if (!d[i].A || !d[i].B || !d[i].C || d[i].ra.d < 1 || d[i].rc.d < 1) return EQF_E_BADARG;
+    // kinds 0, 1: K is a feature width, never empty (an empty batch is M <= 0; for kinds 2, 3 it is K <= 0 and skipped below).
+    // The loaders clamp their addresses to k = K - 1: with K <= 0 they would read in front of the row.
+    if (d[i].kind < 2 && d[i].K < 1) return EQF_E_BADARG;
   }
   static thread_local GXGroup G;
   for (int kind = 0; kind < 2; ++kind) {

@@ -189,6 +189,8 @@ typedef struct eqf_rows {
 
 /* C[i,n] (=|+=) sum_k A[i,k] * B[k,n]  (+ bias[n]).   A: M rows (two-level) x K, B: plain [K,N]
  * with leading dimension ldb, C: M rows (two-level) x N.  accumulate != 0 adds into C.
+ * M <= 0 or N <= 0 is an empty problem (status 0, nothing written); K < 1 is EQF_E_BADARG here and for the kinds 0 and 1
+ * of the grouped calls below, checked for every descriptor before anything is launched.
  * [ref: LinearRS / FullyConnectedTensorProductRescale forward, nets/tensor_product_rescale.py:125-136,171-174;
  *       torch.nn.Linear inside RadialProfile, nets/radial_func.py:46-49] */
 int eqf_gemm_nn(const float* A, eqf_rows ra, const float* B, int ldb, float* C, eqf_rows rc,
