@@ -97,13 +97,12 @@ class matrix_mode:
         return False
 
 
-def _guard_opt(t, dep, what):
+def _guard(t, dep, what):
     """First-order parameter gradient handed out by a create_graph backward: usable as a value, raises when something
     tries to differentiate through it (second derivatives wrt parameters-of-parameters are not implemented)."""
     if t is None:
         return None
     return _Guard.apply(t, dep, what) if dep.requires_grad else t
-
 
 
 def _nonnull(t):
@@ -259,7 +258,7 @@ class _LayerNorm(Function):
         x, weight, rstd, mean0, bias = ctx.saved_tensors
         if torch.is_grad_enabled():  # create_graph: the backward is itself a differentiable HIP operator
             dx, dw, db = _LayerNormBwd.apply(x, weight, dy, rstd, mean0, ctx.layout, ctx.eps, ctx.nb)
-            return dx, _guard_opt(dw, dy, "layer-norm weight gradient"), _guard_opt(db, dy, "layer-norm bias gradient"), \
+            return dx, _guard(dw, dy, "layer-norm weight gradient"), _guard(db, dy, "layer-norm bias gradient"), \
                 None, None
         dy = _c(dy)
         _chk(dy)
@@ -335,7 +334,7 @@ class _AddLayerNorm(Function):
         if torch.is_grad_enabled():  # create_graph: differentiable norm backward + a differentiable add
             dx, dw, db = _LayerNormBwd.apply(s, weight, dy, rstd, mean0, ctx.layout, ctx.eps, ctx.nb)
             d = dx if ds is None else dx + ds
-            return d, d, _guard_opt(dw, dy, "layer-norm weight gradient"), _guard_opt(db, dy, "layer-norm bias gradient"), \
+            return d, d, _guard(dw, dy, "layer-norm weight gradient"), _guard(db, dy, "layer-norm bias gradient"), \
                 None, None
         dy = _c(dy)
         ds = _c(ds) if ds is not None else None
@@ -381,9 +380,34 @@ class LinearSpec:
         # bias gradient -- invisible with zero-initialised biases, 11 % on the OC20 auxiliary head with filled ones)
         j0 = out_layout.seg_index(0, 1)
         self.bias_out_off = out_layout.offsets[j0] if j0 is not None else None
+        # the bias gradient rides in the weight-gradient launch when the pair that writes 0e carries the whole bias
+        self.fuses_bias = any(self.has_bias(l, o) and N == self.bias_dim for (l, _, _, o, N, _) in self.pairs)
 
     def has_bias(self, l, out_off):
         return l == 0 and out_off == self.bias_out_off
+
+    # the plan of `_Linear` (see there)
+    defers = True  # node-row weight gradients may be queued until the backward pass ends (_defer_wgrad)
+    input = staticmethod(_c)
+
+    def fwd(self, x, weight, bias):
+        assert x.shape[1] == self.in_layout.dim and weight.numel() == self.weight_numel
+        return _lin_fwd_descs(x, weight, bias, self)
+
+    def dgrad(self, dy, weight):
+        return _lin_dgrad_descs(dy, weight, self)
+
+    def wgrad(self, x, dy, dw, db):
+        return _lin_wgrad_descs(x, dy, self, dw, db)
+
+    def width(self, weight):
+        return self.out_layout.dim
+
+    def weight_shape(self, x, dy):
+        return (self.weight_numel,)
+
+    def bias_block(self, dy):
+        return self.bias_out_off, self.bias_dim
 
 
 # per-degree / dense linears on the bf16 matrix cores (csrc/gemmx.hip) in every matrix mode but "fp32"; the switch exists for
@@ -493,10 +517,6 @@ class _TaskQueue:
 
 
 _task_queues = weakref.WeakValueDictionary()  # graph task id -> _TaskQueue (kept alive by that task's engine callback only)
-
-
-def note_create_graph():
-    """called by the create_graph branches of the operators' backward (kept for callers; deferral keys on the grad mode itself)"""
 
 
 def set_deferred_weight_gradients(on):
@@ -612,6 +632,20 @@ def _defer_lin_wgrad(w, b, x, dy, spec, fused_b, dw, db):
     _defer_stats["queued"] += 1
 
 
+def _launch(built):
+    """(result, descriptors) of a plan's builder -> result, after ONE grouped launch of the descriptors"""
+    _gemm_group(built[1], _stream())
+    return built[0]
+
+
+def _lin_fwd(x, weight, bias, spec):
+    return _launch(_lin_fwd_descs(x, weight, bias, spec))
+
+
+def _lin_dgrad(dy, weight, spec):
+    return _launch(_lin_dgrad_descs(dy, weight, spec))
+
+
 def _lin_wgrad(x, dy, spec, dw, db=None):
     """dw (flat, zero-initialised by the caller) += x^T dy per degree; db (zero-initialised, optional) += the column
     sums of the scalar block of dy, accumulated by the same launch while dy is staged."""
@@ -619,257 +653,139 @@ def _lin_wgrad(x, dy, spec, dw, db=None):
     return dw
 
 
-class _LinDgrad(Function):
-    """dx = dy W^T as a differentiable op (used only when the backward runs with create_graph=True)."""
+# ------------------------------------------------------------------------------------------------- grouped / dense linear
+def _glin_fwd_descs(x, ldx, K, wide, Ws, bs):
+    """y_g = x[:, g K:(g+1) K] W_g^T (+ b_g), W_g [N_g, K]: (one [rows, sum N] tensor if `wide`, else a tuple; descriptors).
+    `ldx` is the row stride of x."""
+    G = len(Ws)
+    rows_n = x.shape[0]
+    Ns = [int(W.shape[0]) for W in Ws]
+    if wide:
+        out = torch.empty((rows_n, sum(Ns)), device=x.device, dtype=torch.float32)
+        outs, ldo, offs = [out] * G, sum(Ns), [sum(Ns[:g]) for g in range(G)]
+    else:
+        outs = [torch.empty((rows_n, n), device=x.device, dtype=torch.float32) for n in Ns]
+        ldo, offs = None, [0] * G
+    descs = [_desc(1, (x, g * K), rows(1, ldx, 0), (Ws[g], 0), K, (outs[g], offs[g]),
+                   rows(1, ldo if wide else Ns[g], 0), bs[g], rows_n, Ns[g], K) for g in range(G)]
+    return (out if wide else tuple(outs)), descs
+
+
+def _glin_dgrad_descs(dyt, offs, ldd, Ws, K, rows_n):
+    """dx[:, g K:(g+1) K] = dy_g W_g"""
+    G = len(Ws)
+    Ns = [int(W.shape[0]) for W in Ws]
+    dx = torch.empty((rows_n, G * K), device=dyt[0].device, dtype=torch.float32)
+    return dx, [_desc(0, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else Ns[g], 0), (Ws[g], 0), K, (dx, g * K),
+                      rows(1, G * K, 0), None, rows_n, K, Ns[g]) for g in range(G)]
+
+
+def _glin_wgrad_descs(dyt, offs, ldd, x, ldx, K, dWs, dbs):
+    """dW_g[N_g, K] (zero-initialised) += dy_g^T x_g; db_g (zero-initialised, optional) += column sums of dy_g (same launch).
+    (kind 3: `rc` carries the row stride of x and ldb the leading dimension of dW_g)"""
+    return [_desc(3, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else dW.shape[0], 0), (x, g * K), K, (dW, 0),
+                  rows(1, ldx, 0), dbs[g], dW.shape[0], K, x.shape[0]) for g, dW in enumerate(dWs)]
+
+
+class _DensePlan:
+    """torch.nn.Linear (y = x W^T + b, W [N, K]) as a plan of `_Linear`: the grouped linear's descriptors with one group.
+    Its input may be a column block of a wider row-major tensor, read in place (the radial bank's hidden rows)."""
+    defers = False      # only the per-degree (node-row) weight gradients are queued
+    fuses_bias = True   # the bias gradient rides in the weight-gradient launch
 
     @staticmethod
-    def forward(ctx, dy, weight, spec):
-        dy, weight = _c(dy), _c(weight)
-        _chk(dy, weight)
-        ctx.save_for_backward(dy, weight)
-        ctx.spec = spec
-        return _lin_dgrad(dy, weight, spec)
+    def input(x):
+        if (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % 4 == 0
+                and x.storage_offset() % 4 == 0):
+            return x
+        return _c(x)
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, c):
-        dy, weight = ctx.saved_tensors
-        c = _c(c)
-        _chk(c)
-        g_dy = _lin_fwd(c, weight, None, ctx.spec) if ctx.needs_input_grad[0] else None
-        g_w = None
-        if ctx.needs_input_grad[1]:
-            g_w = _lin_wgrad(c, dy, ctx.spec, _zeros_like(weight))
-        return g_dy, g_w, None
-
-
-class _LinWgrad(Function):
-    """dW = x^T dy as a differentiable op (create_graph only)."""
+    def fwd(x, W, b):
+        return _glin_fwd_descs(x, x.stride(0), x.shape[1], True, (W,), (b,))
 
     @staticmethod
-    def forward(ctx, x, dy, spec):
-        x, dy = _c(x), _c(dy)
-        _chk(x, dy)
-        ctx.save_for_backward(x, dy)
-        ctx.spec = spec
-        return _lin_wgrad(x, dy, spec, _zeros(spec.weight_numel, device=x.device, dtype=torch.float32))
+    def dgrad(dy, W):
+        return _glin_dgrad_descs((dy,), (0,), dy.shape[1], (W,), W.shape[1], dy.shape[0])
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, c):
-        x, dy = ctx.saved_tensors
-        c = _c(c)
-        _chk(c)
-        g_x = _lin_dgrad(dy, c, ctx.spec) if ctx.needs_input_grad[0] else None
-        g_dy = _lin_fwd(x, c, None, ctx.spec) if ctx.needs_input_grad[1] else None
-        return g_x, g_dy, None
-
-
-class _IrrepsLinear(Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, spec):
-        x = _c(x)
-        weight = _c(weight)
-        _chk(x, weight, bias)
-        Din = spec.in_layout.dim
-        assert x.shape[1] == Din and weight.numel() == spec.weight_numel
-        out = _lin_fwd(x, weight, bias, spec)
-        ctx.save_for_backward(x, weight)
-        ctx.spec = spec
-        ctx.has_bias = bias is not None
-        ctx.bias_param = bias if (bias is not None and bias.is_leaf) else None  # (identity only: for the deferred gradients)
-        return out
+    def wgrad(x, dy, dw, db):
+        return _glin_wgrad_descs((dy,), (0,), dy.shape[1], x, x.stride(0), x.shape[1], (dw,), (db,))
 
     @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        spec = ctx.spec
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if torch.is_grad_enabled():  # create_graph: every piece is itself differentiable
-            note_create_graph()
-            dx = _LinDgrad.apply(dy, weight, spec) if ctx.needs_input_grad[0] else None
-            if not _want_param_grads():
-                return dx, None, None, None
-            dw = _LinWgrad.apply(x, dy, spec) if ctx.needs_input_grad[1] else None
-            db = None
-            if want_b:
-                j = spec.out_layout.seg_index(0)
-                o = spec.out_layout.offsets[j]
-                db = dy[:, o:o + spec.bias_dim].sum(0)
-            return dx, dw, db, None
-        dy = _c(dy)
-        _chk(dy)
-        n = x.shape[0]
-        Dout = spec.out_layout.dim
-        st = _stream()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _lin_dgrad(dy, weight, spec)
-        if not _want_param_grads():  # force evaluation: d E / d pos only
-            return dx, None, None, None
-        if ctx.needs_input_grad[1] or want_b:
-            dw_, db_ = _zeros2(weight.numel(), spec.bias_dim if want_b else 0, x.device)
-        fused_b = want_b and ctx.needs_input_grad[1] and any(spec.has_bias(l, o) and N == spec.bias_dim
-                                                              for (l, _, _, o, N, _) in spec.pairs)
-        if ctx.needs_input_grad[1]:
-            bp = ctx.bias_param if fused_b else None
-            if _can_defer(weight, bp) and (not fused_b or bp is not None):
-                _defer_lin_wgrad(weight, bp, x, dy, spec, fused_b, dw_, db_)  # (zeros now) filled when backward ends
-                dw = dw_
-            else:
-                dw = _lin_wgrad(x, dy, spec, dw_, db_ if fused_b else None)
-        if want_b:
-            db = db_
-            if not fused_b:
-                j = spec.out_layout.seg_index(0)
-                call("eqf_colsum", _p(dy, spec.out_layout.offsets[j]), rows(1, Dout, 0), n, spec.bias_dim, _p(db), st)
-        return dx, dw, db, None
-
-
-def irreps_linear(x, weight, bias, spec):
-    return _IrrepsLinear.apply(x, weight, bias, spec)
-
-
-class _IrrepsLinearPair(Function):
-    """Two per-degree linears of the SAME input (GraphAttention's merge_src / merge_dst, nets/graph_attention_transformer.py:
-    485-486) with their GEMMs side by side in one launch: forward 1 launch instead of 2, data gradients 1 + one add instead of
-    2 + autograd's add, weight gradients 1 instead of 2 -- these node-row launches cost ~12 us each whatever they compute
-    (tools/gemm_shapes.py).  Under create_graph the backward is the two linears' own differentiable pieces."""
+    def width(W):
+        return W.shape[0]
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, spec1, spec2):
-        x, w1, w2 = _c(x), _c(w1), _c(w2)
-        _chk(x, w1, b1, w2, b2)
-        assert x.shape[1] == spec1.in_layout.dim == spec2.in_layout.dim
-        y1, d1 = _lin_fwd_descs(x, w1, b1, spec1)
-        y2, d2 = _lin_fwd_descs(x, w2, b2, spec2)
-        _gemm_group(d1 + d2, _stream())
-        ctx.save_for_backward(x, w1, w2)
-        ctx.specs = (spec1, spec2)
-        ctx.has_bias = (b1 is not None, b2 is not None)
-        ctx.bias_params = tuple(b if (b is not None and b.is_leaf) else None for b in (b1, b2))
-        return y1, y2
+    def weight_shape(x, dy):
+        return (dy.shape[1], x.shape[1])
 
     @staticmethod
-    def backward(ctx, dy1, dy2):
-        x, w1, w2 = ctx.saved_tensors
-        spec1, spec2 = ctx.specs
-        need = ctx.needs_input_grad  # x, w1, b1, w2, b2
-        ws, specs, dys, hb = (w1, w2), (spec1, spec2), [dy1, dy2], ctx.has_bias
-        for i in (0, 1):
-            if dys[i] is None:
-                dys[i] = _zeros((x.shape[0], specs[i].out_layout.dim), device=x.device, dtype=torch.float32)
-        if torch.is_grad_enabled():  # create_graph: every piece is itself differentiable
-            note_create_graph()
-            dx = None
-            if need[0]:
-                dx = _LinDgrad.apply(dys[0], w1, spec1) + _LinDgrad.apply(dys[1], w2, spec2)
-            if not _want_param_grads():
-                return dx, None, None, None, None, None, None
-            out = [dx]
-            for i in (0, 1):
-                out.append(_LinWgrad.apply(x, dys[i], specs[i]) if need[1 + 2 * i] else None)
-                db = None
-                if hb[i] and need[2 + 2 * i]:
-                    o = specs[i].out_layout.offsets[specs[i].out_layout.seg_index(0)]
-                    db = dys[i][:, o:o + specs[i].bias_dim].sum(0)
-                out.append(db)
-            return tuple(out) + (None, None)
-        dys = [_c(d) for d in dys]
-        _chk(*dys)
-        st = _stream()
-        dx = None
-        if need[0]:
-            dxa, da = _lin_dgrad_descs(dys[0], w1, spec1)
-            dxb, db_ = _lin_dgrad_descs(dys[1], w2, spec2)
-            _gemm_group(da + db_, st)
-            dx = dxa.add_(dxb)
-        if not _want_param_grads():
-            return dx, None, None, None, None, None, None
-        grads = [None, None, None, None]  # dw1, db1, dw2, db2
-        descs, late = [], []
-        for i in (0, 1):
-            want_b = hb[i] and need[2 + 2 * i]
-            if not (need[1 + 2 * i] or want_b):
-                continue
-            dw_, dbv = _zeros2(ws[i].numel(), specs[i].bias_dim if want_b else 0, x.device)
-            fused_b = want_b and need[1 + 2 * i] and any(specs[i].has_bias(l, o) and N == specs[i].bias_dim
-                                                         for (l, _, _, o, N, _) in specs[i].pairs)
-            if need[1 + 2 * i]:
-                bp = ctx.bias_params[i] if fused_b else None
-                if _can_defer(ws[i], bp) and (not fused_b or bp is not None):
-                    _defer_lin_wgrad(ws[i], bp, x, dys[i], specs[i], fused_b, dw_, dbv)
-                else:
-                    descs += _lin_wgrad_descs(x, dys[i], specs[i], dw_, dbv if fused_b else None)
-                grads[2 * i] = dw_
-            if want_b:
-                grads[2 * i + 1] = dbv
-                if not fused_b:
-                    late.append((i, dbv))
-        if descs:
-            _gemm_group(descs, st)
-        for i, dbv in late:
-            o = specs[i].out_layout.offsets[specs[i].out_layout.seg_index(0)]
-            call("eqf_colsum", _p(dys[i], o), rows(1, specs[i].out_layout.dim, 0), x.shape[0], specs[i].bias_dim, _p(dbv), st)
-        return dx, grads[0], grads[1], grads[2], grads[3], None, None
+    def bias_block(dy):
+        return 0, dy.shape[1]
 
 
-def irreps_linear_pair(x, w1, b1, spec1, w2, b2, spec2):
-    return _IrrepsLinearPair.apply(x, w1, b1, w2, b2, spec1, spec2)
+_dense = _DensePlan()
+_DENSE = (_dense,)  # the plans of dense_linear
 
 
 def _dense_fwd(x, weight, bias):
-    M, K = x.shape
-    N = weight.shape[0]
-    y = torch.empty((M, N), device=x.device, dtype=torch.float32)
-    # (x may be a column block of a wider row-major tensor: row stride x.stride(0), read in place)
-    _gemm_group([_desc(1, (x, 0), rows(1, x.stride(0), 0), (weight, 0), K, (y, 0), rows(1, N, 0), bias, M, N, K)], _stream())
-    return y
+    return _launch(_dense.fwd(x, weight, bias))
 
 
 def _dense_dgrad(dy, weight):
-    M, N = dy.shape
-    K = weight.shape[1]
-    dx = torch.empty((M, K), device=dy.device, dtype=torch.float32)
-    _gemm_group([_desc(0, (dy, 0), rows(1, N, 0), (weight, 0), K, (dx, 0), rows(1, K, 0), None, M, K, N)], _stream())
-    return dx
+    return _launch(_dense.dgrad(dy, weight))
 
 
 def _dense_wgrad(x, dy, dw, db=None):
-    """dw [N, K] (zero-initialised) += dy^T x; db [N] (zero-initialised, optional) += column sums of dy (same launch)"""
-    M, K = x.shape
-    N = dy.shape[1]
-    # (kind 3: `rc` carries the row stride of x -- possibly a column block of a wider tensor -- and ldb the leading dimension of dw)
-    _gemm_group([_desc(3, (dy, 0), rows(1, N, 0), (x, 0), K, (dw, 0), rows(1, x.stride(0), 0), db, N, K, M)], _stream())
+    _gemm_group(_dense.wgrad(x, dy, dw, db), _stream())
     return dw
 
 
-class _DenseDgrad(Function):
+# ------------------------------------------------------------------------------------------------- the linear operator
+# A PLAN is the only part of a linear that knows shapes: `LinearSpec` (per-degree GEMMs between two row layouts) and
+# `_DensePlan`.  It builds the descriptors of the forward (fwd), the data gradient (dgrad) and the weight gradient (wgrad),
+# says where the bias gradient sits in dy (bias_block), whether it can ride in the weight-gradient launch (fuses_bias) and
+# whether the weight gradient may be queued (defers).  Everything else -- first order, the force pass, create_graph, the
+# accumulators, eqf_colsum, deferral -- is written once, in the three Functions below.
+class _LinearDgrad(Function):
+    """dx = dy W^T as a differentiable op (used only when the backward runs with create_graph=True)."""
+
     @staticmethod
-    def forward(ctx, dy, weight):
+    def forward(ctx, dy, weight, plan):
         dy, weight = _c(dy), _c(weight)
         _chk(dy, weight)
         ctx.save_for_backward(dy, weight)
-        return _dense_dgrad(dy, weight)
+        ctx.plan = plan
+        return _launch(plan.dgrad(dy, weight))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, c):
         dy, weight = ctx.saved_tensors
+        plan = ctx.plan
         c = _c(c)
         _chk(c)
-        g_dy = _dense_fwd(c, weight, None) if ctx.needs_input_grad[0] else None
-        g_w = _dense_wgrad(c, dy, _zeros_like(weight)) if ctx.needs_input_grad[1] else None
-        return g_dy, g_w
+        g_dy = _launch(plan.fwd(c, weight, None)) if ctx.needs_input_grad[0] else None
+        g_w = None
+        if ctx.needs_input_grad[1]:
+            g_w = _zeros_like(weight)
+            _gemm_group(plan.wgrad(c, dy, g_w, None), _stream())
+        return g_dy, g_w, None
 
 
-class _DenseWgrad(Function):
+class _LinearWgrad(Function):
+    """dW = x^T dy as a differentiable op (create_graph only)."""
+
     @staticmethod
-    def forward(ctx, x, dy):
+    def forward(ctx, x, dy, plan):
         x, dy = _c(x), _c(dy)
         _chk(x, dy)
         ctx.save_for_backward(x, dy)
-        return _dense_wgrad(x, dy, _zeros((dy.shape[1], x.shape[1]), device=x.device, dtype=torch.float32))
+        ctx.plan = plan
+        dw = _zeros(plan.weight_shape(x, dy), device=x.device, dtype=torch.float32)
+        _gemm_group(plan.wgrad(x, dy, dw, None), _stream())
+        return dw
 
     @staticmethod
     @once_differentiable
@@ -877,60 +793,114 @@ class _DenseWgrad(Function):
         x, dy = ctx.saved_tensors
         c = _c(c)
         _chk(c)
-        g_x = _dense_dgrad(dy, c) if ctx.needs_input_grad[0] else None
-        g_dy = _dense_fwd(x, c, None) if ctx.needs_input_grad[1] else None
-        return g_x, g_dy
+        g_x = _launch(ctx.plan.dgrad(dy, c)) if ctx.needs_input_grad[0] else None
+        g_dy = _launch(ctx.plan.fwd(x, c, None)) if ctx.needs_input_grad[1] else None
+        return g_x, g_dy, None
 
 
-class _DenseLinear(Function):
-    """torch.nn.Linear semantics (y = x W^T + b) on the exact-fp32 MFMA path."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % 4 == 0
-                and x.storage_offset() % 4 == 0):  # (a column block of a wider tensor is read in place: the radial bank's hidden rows)
-            x = _c(x)
-        weight = _c(weight)
-        _chk(x if x.is_contiguous() else x[:1, :1], weight, bias)  # (device / dtype of a row-strided x through its corner)
-        y = _dense_fwd(x, weight, bias)
-        ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        return y
+class _Linear(Function):
+    """n linears of ONE input, each with its plan, weight and optional bias: params = (W_0, b_0, W_1, b_1, ...).  Their
+    GEMMs go side by side: ONE launch in forward, one for the data gradients (plus an in-place add per further member), one
+    for the weight gradients -- these node-row launches cost ~12 us each whatever they compute (tools/gemm_shapes.py).
+    n = 2 is GraphAttention's merge_src / merge_dst (nets/graph_attention_transformer.py:485-486).  Under create_graph the
+    backward is made of the members' differentiable pieces."""
 
     @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if torch.is_grad_enabled():  # create_graph
-            dx = _DenseDgrad.apply(dy, weight) if ctx.needs_input_grad[0] else None
+    def forward(ctx, x, plans, *params):
+        x = plans[0].input(x)
+        Ws, bs = [_c(W) for W in params[0::2]], params[1::2]
+        _chk(x if x.is_contiguous() else x[:1, :1], *Ws, *bs)  # (device / dtype of a row-strided x through its corner)
+        outs, descs = [], []
+        for plan, W, b in zip(plans, Ws, bs):
+            y, d = plan.fwd(x, W, b)
+            outs.append(y)
+            descs += d
+        _gemm_group(descs, _stream())
+        ctx.save_for_backward(x, *Ws)
+        ctx.plans = plans
+        ctx.has_bias = [b is not None for b in bs]
+        ctx.bias_params = [b if (b is not None and b.is_leaf) else None for b in bs]  # (identity only: for the deferred gradients)
+        return outs[0] if len(outs) == 1 else tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        x, *Ws = ctx.saved_tensors
+        plans, need = ctx.plans, ctx.needs_input_grad  # x, plans, W_0, b_0, W_1, b_1, ...
+        members = range(len(plans))
+        dys = [dy if dy is not None else _zeros((x.shape[0], plans[i].width(Ws[i])), device=x.device, dtype=torch.float32)
+               for i, dy in enumerate(dys)]
+        want_w = [need[2 + 2 * i] for i in members]
+        want_b = [ctx.has_bias[i] and need[3 + 2 * i] for i in members]
+        grads = [None, None]
+        if torch.is_grad_enabled():  # create_graph: every piece is itself differentiable
+            if need[0]:
+                for i in members:
+                    piece = _LinearDgrad.apply(dys[i], Ws[i], plans[i])
+                    grads[0] = piece if i == 0 else grads[0] + piece
             if not _want_param_grads():
-                return dx, None, None
-            dw = _DenseWgrad.apply(x, dy) if ctx.needs_input_grad[1] else None
-            db = dy.sum(0) if want_b else None
-            return dx, dw, db
-        dy = _c(dy)
-        _chk(dy)
-        M, K = x.shape
-        N = weight.shape[0]
+                return tuple(grads) + (None,) * (2 * len(plans))
+            for i in members:
+                grads.append(_LinearWgrad.apply(x, dys[i], plans[i]) if want_w[i] else None)
+                db = None
+                if want_b[i]:
+                    o, nb = plans[i].bias_block(dys[i])
+                    db = (dys[i] if nb == dys[i].shape[1] else dys[i][:, o:o + nb]).sum(0)
+                grads.append(db)
+            return tuple(grads)
+        dys = [_c(dy) for dy in dys]
+        _chk(*dys)
         st = _stream()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _dense_dgrad(dy, weight)
-        if not _want_param_grads():  # force evaluation
-            return dx, None, None
-        if ctx.needs_input_grad[1] or want_b:
-            dw_, db_ = _zeros2(weight.numel(), N if want_b else 0, x.device)
-        if ctx.needs_input_grad[1]:
-            dw = _dense_wgrad(x, dy, dw_.view_as(weight), db_ if want_b else None)
-        if want_b:
-            db = db_
-            if not ctx.needs_input_grad[1]:
-                call("eqf_colsum", _p(dy), rows(1, N, 0), M, N, _p(db), st)
-        return dx, dw, db
+        if need[0]:
+            pieces, descs = [], []
+            for i in members:
+                piece, d = plans[i].dgrad(dys[i], Ws[i])
+                pieces.append(piece)
+                descs += d
+            _gemm_group(descs, st)
+            grads[0] = pieces[0]
+            for piece in pieces[1:]:
+                grads[0].add_(piece)
+        if not _want_param_grads():  # force evaluation: d E / d pos only
+            return tuple(grads) + (None,) * (2 * len(plans))
+        descs, late = [], []
+        for i in members:
+            plan, W, dy = plans[i], Ws[i], dys[i]
+            dw = db = None
+            if want_w[i] or want_b[i]:
+                o, nb = plan.bias_block(dy)
+                dw_, db_ = _zeros(tuple(W.shape), x.device), _zeros(nb if want_b[i] else 0, x.device)
+                fused = want_b[i] and want_w[i] and plan.fuses_bias
+                if want_w[i]:
+                    dw = dw_
+                    bp = ctx.bias_params[i] if fused else None  # (a fused bias defers only together with a leaf bias parameter)
+                    if plan.defers and (not fused or bp is not None) and _can_defer(W, bp):
+                        _defer_lin_wgrad(W, bp, x, dy, plan, fused, dw_, db_)  # (zeros now) filled when backward ends
+                    else:
+                        descs += plan.wgrad(x, dy, dw_, db_ if fused else None)
+                if want_b[i]:
+                    db = db_
+                    if not fused:
+                        late.append((dy, o, nb, db_))
+            grads += [dw, db]
+        if descs:
+            _gemm_group(descs, st)
+        for dy, o, nb, db in late:
+            call("eqf_colsum", _p(dy, o), rows(1, dy.shape[1], 0), dy.shape[0], nb, _p(db), st)
+        return tuple(grads)
+
+
+def irreps_linear(x, weight, bias, spec):
+    return _Linear.apply(x, (spec,), weight, bias)
+
+
+def irreps_linear_pair(x, w1, b1, spec1, w2, b2, spec2):
+    """two per-degree linears of the same input (different output layouts allowed) in one launch per direction"""
+    return _Linear.apply(x, (spec1, spec2), w1, b1, w2, b2)
 
 
 def dense_linear(x, weight, bias=None):
-    return _DenseLinear.apply(x, weight, bias)
+    """torch.nn.Linear semantics (y = x W^T + b)"""
+    return _Linear.apply(x, _DENSE, weight, bias)
 
 
 def split_columns(x, G):
@@ -1063,7 +1033,7 @@ class _LnSilu(Function):
         G = ctx.groups
         if torch.is_grad_enabled():  # create_graph
             dx, dg, db = _LnSiluBwd.apply(x, gamma, beta, dy, ctx.eps, G)
-            return dx, _guard_opt(dg, dy, "LayerNorm weight gradient"), _guard_opt(db, dy, "LayerNorm bias gradient"), \
+            return dx, _guard(dg, dy, "LayerNorm weight gradient"), _guard(db, dy, "LayerNorm bias gradient"), \
                 None, None
         dy = _c(dy)
         _chk(dy)
@@ -1123,47 +1093,25 @@ def _glin_views(dys, wide, Ns, rows_n, dev):
 
 
 def _glin_fwd(x, K, wide, Ws, bs):
-    """y_g = x[:, g K:(g+1) K] W_g^T (+ b_g) for all g in one launch; one [rows, sum N] tensor if `wide`, else a tuple"""
-    G = len(Ws)
-    rows_n, ldx = x.shape
-    Ns = [int(W.shape[0]) for W in Ws]
-    if wide:
-        out = torch.empty((rows_n, sum(Ns)), device=x.device, dtype=torch.float32)
-        outs, ldo, offs = [out] * G, sum(Ns), [sum(Ns[:g]) for g in range(G)]
-    else:
-        outs = [torch.empty((rows_n, n), device=x.device, dtype=torch.float32) for n in Ns]
-        ldo, offs = None, [0] * G
-    descs = [_desc(1, (x, g * K), rows(1, ldx, 0), (Ws[g], 0), K, (outs[g], offs[g]),
-                   rows(1, ldo if wide else Ns[g], 0), bs[g], rows_n, Ns[g], K) for g in range(G)]
-    _gemm_group(descs, _stream())
-    return out if wide else tuple(outs)
+    return _launch(_glin_fwd_descs(x, x.shape[1], K, wide, Ws, bs))
 
 
 def _glin_dgrad(dyt, offs, ldd, Ws, K, rows_n):
-    """dx[:, g K:(g+1) K] = dy_g W_g"""
-    G = len(Ws)
-    Ns = [int(W.shape[0]) for W in Ws]
-    dx = torch.empty((rows_n, G * K), device=dyt[0].device, dtype=torch.float32)
-    _gemm_group([_desc(0, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else Ns[g], 0), (Ws[g], 0), K, (dx, g * K),
-                       rows(1, G * K, 0), None, rows_n, K, Ns[g]) for g in range(G)], _stream())
-    return dx
+    return _launch(_glin_dgrad_descs(dyt, offs, ldd, Ws, K, rows_n))
 
 
 def _glin_wgrad(dyt, offs, ldd, x, K, Ns, has_b):
-    """dW_g[N_g, K] = dy_g^T x_g, db_g = column sums of dy_g (same launch); one zero-filled flat buffer behind all of them"""
-    G = len(Ns)
-    rows_n, ldx = x.shape
-    sizes = [n * K for n in Ns] + [n if hb else 0 for n, hb in zip(Ns, has_b)]
-    flat = _zeros(sum(sizes), x.device)
+    """(dW_g, db_g or None) of all groups in one launch; one zero-filled flat buffer behind all of them (a captured step counts
+    fill nodes)"""
+    flat = _zeros(sum(n * K for n in Ns) + sum(n for n, hb in zip(Ns, has_b) if hb), x.device)
     o, dWs, dbs = 0, [], []
-    for g in range(G):
-        dWs.append(flat[o:o + Ns[g] * K].view(Ns[g], K))
-        o += Ns[g] * K
-    for g in range(G):
-        dbs.append(flat[o:o + Ns[g]] if has_b[g] else None)
-        o += Ns[g] if has_b[g] else 0
-    _gemm_group([_desc(3, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else Ns[g], 0), (x, g * K), K, (dWs[g], 0),
-                       rows(1, ldx, 0), dbs[g], Ns[g], K, rows_n) for g in range(G)], _stream())
+    for n in Ns:
+        dWs.append(flat[o:o + n * K].view(n, K))
+        o += n * K
+    for n, hb in zip(Ns, has_b):
+        dbs.append(flat[o:o + n] if hb else None)
+        o += n if hb else 0
+    _gemm_group(_glin_wgrad_descs(dyt, offs, ldd, x, x.shape[1], K, dWs, dbs), _stream())
     return dWs, dbs
 
 
@@ -1614,7 +1562,7 @@ class _RbfGaussian(Function):
         length, mean, std, weight, bias = ctx.saved_tensors
         if torch.is_grad_enabled() and ctx.needs_input_grad[0]:  # create_graph (forces of a gaussian-basis MD17 model)
             outs = _RbfGaussianBwd.apply(length, mean, std, weight, bias, dout, ctx.cutoff)
-            return (outs[0],) + tuple(_guard_opt(t, dout, "radial-basis parameter gradient") for t in outs[1:]) + (None,)
+            return (outs[0],) + tuple(_guard(t, dout, "radial-basis parameter gradient") for t in outs[1:]) + (None,)
         dout = _c(dout)
         _chk(dout)
         return _rbf_gaussian_bwd(length, mean, std, weight, bias, dout, ctx.cutoff, ctx.needs_input_grad[0]) + (None,)
@@ -1764,7 +1712,7 @@ class _RbfBessel(Function):
         length, freq = ctx.saved_tensors
         if torch.is_grad_enabled() and ctx.needs_input_grad[0]:  # create_graph
             dlen, dfreq = _RbfBesselBwd.apply(length, freq, dout, ctx.cutoff)
-            return dlen, _guard_opt(dfreq, dout, "Bessel frequency gradient"), None
+            return dlen, _guard(dfreq, dout, "Bessel frequency gradient"), None
         dout = _c(dout)
         _chk(dout)
         dlen = torch.empty_like(length) if ctx.needs_input_grad[0] else None
@@ -2113,10 +2061,6 @@ class _Guard(Function):
         raise NotImplementedError("second-order differentiation through the %s is not implemented" % ctx.what)
 
 
-def _guard(t, dep, what):
-    return _Guard.apply(t, dep, what) if dep.requires_grad else t
-
-
 _side_streams = {}
 # weight gradient of the fused SeparableFCTP on a side stream beside its data gradient: measured +1 % on the QM9 step (14.00 vs
 # 14.15 ms, profiles/r03) -- the data-gradient kernel holds the whole register file of its SIMDs, so little co-resides -- and
@@ -2304,7 +2248,6 @@ class _SepFctp(Function):
         st = _stream()
         dev = x.device
         if torch.is_grad_enabled():  # create_graph: differentiable data-gradient (forces); see _SepFctpBwdData
-            note_create_graph()
             need = ctx.needs_input_grad
             if d1 is None:
                 d1 = _zeros((E, spec.out_layout.dim), device=dev, dtype=torch.float32)
@@ -2422,7 +2365,6 @@ class _SepFctpGated(Function):
         E = x_raw.shape[0]
         dev = x_raw.device
         if torch.is_grad_enabled():  # create_graph: the separate differentiable operators, on the re-materialised gate output
-            note_create_graph()
             xg = gate(x_raw, S, gated_layout, c_silu, c_sig)
             outs = _SepFctpBwdData.apply(xg, coupling, w, weight, None, d1, None, spec, mode, ctx.packed)
             dxg, dM = outs[0], outs[1]
@@ -2514,7 +2456,7 @@ class _AlphaLogits(Function):
         H, Kh, c = ctx.args
         if torch.is_grad_enabled():  # create_graph
             da, dd = _AlphaLogitsBwd.apply(a, alpha_dot, dlogit, H, Kh, c)
-            return da, _guard_opt(dd, dlogit, "alpha_dot gradient"), None, None, None
+            return da, _guard(dd, dlogit, "alpha_dot gradient"), None, None, None
         dlogit = _c(dlogit)
         _chk(dlogit)
         da = torch.empty_like(a)

@@ -28,7 +28,7 @@ def _queued():
 
 
 class _Lin(torch.autograd.Function):
-    """y = x w (CPU stand-in for _IrrepsLinear): its backward hands the weight gradient to the deferral queue when allowed"""
+    """y = x w (CPU stand-in for ops._Linear): its backward hands the weight gradient to the deferral queue when allowed"""
 
     @staticmethod
     def forward(ctx, x, w, tag, fail):
