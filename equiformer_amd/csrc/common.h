@@ -61,3 +61,10 @@ __host__ __device__ inline int irreps_dim(const eqf_irreps& ir) {
   for (int s = 0; s < ir.nseg; ++s) D += ir.mul[s] * (2 * ir.l[s] + 1);
   return D;
 }
+
+// output irrep of a path: l3[p] = degree (+ EQF_L3_ODD for an odd-parity output segment of an E(3) table)
+__host__ __device__ inline int path_l3(const eqf_dtp_paths& P, int p) { return P.l3[p] & (EQF_L3_ODD - 1); }
+__host__ __device__ inline int path_odd(const eqf_dtp_paths& P, int p) { return (P.l3[p] & EQF_L3_ODD) ? 1 : 0; }
+// slot of the output segment (l, parity) in the host arrays of per-segment weight pointers (Wl, dWl: 8 entries): even
+// segments sit at l -- the arrays of an SE(3) operator are indexed by degree as ever --, odd ones at 4 + l (l <= 3)
+inline int seg_slot(int l, int odd) { return odd ? 4 + l : l; }

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void coupling_fwd_kernel(const float* __restri
   if (idx >= total) return;
   const long e = idx / P.npaths;
   const int p = (int)(idx - e * P.npaths);
-  const int d1 = 2 * P.l1[p] + 1, d2 = 2 * P.l2[p] + 1, d3 = 2 * P.l3[p] + 1;
+  const int d1 = 2 * P.l1[p] + 1, d2 = 2 * P.l2[p] + 1, d3 = 2 * path_l3(P, p) + 1;
   const float* y = sh + e * P.sh_dim + P.l2[p] * P.l2[p];
   const float* c = cg + P.cg_off[p];
   float* m = M + e * P.m_numel + P.m_off[p];
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void coupling_bwd_kernel(const float* __restri
   float acc = 0.f;
   for (int p = 0; p < P.npaths; ++p) {
     if (P.l2[p] != l2) continue;
-    const int d1 = 2 * P.l1[p] + 1, d2 = 2 * l2 + 1, d3 = 2 * P.l3[p] + 1;
+    const int d1 = 2 * P.l1[p] + 1, d2 = 2 * l2 + 1, d3 = 2 * path_l3(P, p) + 1;
     const float* c = cg + P.cg_off[p];
     const float* g = dM + e * P.m_numel + P.m_off[p];
     for (int i = 0; i < d1; ++i)
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void dtp_fwd_kernel(const float* __restrict__ 
   int p = 0;
   while (p + 1 < P.npaths && item >= P.w_off[p + 1]) ++p;
   const int u = item - P.w_off[p];
-  const int d1 = 2 * P.l1[p] + 1, d3 = 2 * P.l3[p] + 1;
+  const int d1 = 2 * P.l1[p] + 1, d3 = 2 * path_l3(P, p) + 1;
   const float wv = w ? w[e * P.w_numel + item] : 1.f;
   const float* xp = x + e * P.in_dim + P.in_off[p] + u;
   const float* mp = M + e * P.m_numel + P.m_off[p];
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void dtp_bwd_kernel(const float* __restrict__ 
     }
     for (int p = 0; p < P.npaths; ++p) {
       if (P.in_off[p] != in_off) continue;
-      const int d3 = 2 * P.l3[p] + 1;
+      const int d3 = 2 * path_l3(P, p) + 1;
       const float wv = w ? w[e * P.w_numel + P.w_off[p] + u] : 1.f;
       const float* mp = M + e * P.m_numel + P.m_off[p];
       const float* gp = d_out + e * P.out_dim + P.out_off[p] + P.out_ch[p] + u;

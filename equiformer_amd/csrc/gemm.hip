@@ -638,10 +638,10 @@ int launch_tn(TnArgs& a, hipStream_t st) {
   return 0;
 }
 
-// Build the per-slab table of output degree l3; returns K (channels of that degree) or <0 on error.
+// Build the per-slab table of the output segment (l3, parity); returns K (channels of that degree) or <0 on error.
 // The coupling row is laid out degree-major (layout.DtpTable), so the matrices of all paths that feed l3 form one
 // contiguous block [m_base, m_base + m_len).
-int build_dtp(const eqf_dtp_paths* P, int l3, const float* x, const float* coupling, const float* w, DtpA& D) {
+int build_dtp(const eqf_dtp_paths* P, int l3, int odd, const float* x, const float* coupling, const float* w, DtpA& D) {
   D.x = x;
   D.coupling = coupling;
   D.w = w;
@@ -651,7 +651,7 @@ int build_dtp(const eqf_dtp_paths* P, int l3, const float* x, const float* coupl
   D.d3 = 2 * l3 + 1;
   int K = 0, m_lo = 1 << 30, m_hi = 0;
   for (int p = 0; p < P->npaths; ++p)
-    if (P->l3[p] == l3) {
+    if (path_l3(*P, p) == l3 && path_odd(*P, p) == odd) {
       K = P->out_k[p];
       const int len = (2 * P->l1[p] + 1) * (2 * l3 + 1);
       if (P->m_off[p] < m_lo) m_lo = P->m_off[p];
@@ -664,7 +664,7 @@ int build_dtp(const eqf_dtp_paths* P, int l3, const float* x, const float* coupl
   int m_sum = 0;
   for (int s = 0; s < K / 32; ++s) D.slabs[s].d1 = 0;
   for (int p = 0; p < P->npaths; ++p) {
-    if (P->l3[p] != l3) continue;
+    if (path_l3(*P, p) != l3 || path_odd(*P, p) != odd) continue;
     if (P->mul[p] % 32 != 0 || P->out_ch[p] % 32 != 0) return EQF_E_UNSUPPORTED;
     if (P->l1[p] > 3) return EQF_E_UNSUPPORTED;
     m_sum += (2 * P->l1[p] + 1) * (2 * l3 + 1);
@@ -844,17 +844,19 @@ int eqf_dtp_linear_fwd(const float* x, const float* coupling, const float* w, co
   const int Dout = irreps_dim(*out_irreps);
   int off = 0;
   for (int s = 0; s < out_irreps->nseg; ++s) {
-    const int l3 = out_irreps->l[s], N = out_irreps->mul[s], d3 = 2 * l3 + 1;
+    const int l3 = out_irreps->l[s], odd = out_irreps->odd[s] ? 1 : 0, N = out_irreps->mul[s], d3 = 2 * l3 + 1;
+    if (l3 > 3) return EQF_E_UNSUPPORTED;
+    const float* const Ws = Wl[seg_slot(l3, odd)];
     RowsArgs a{};
-    const int K = build_dtp(paths, l3, x, coupling, w, a.dtp);
+    const int K = build_dtp(paths, l3, odd, x, coupling, w, a.dtp);
     if (K < 0) return K;
-    if (K == 0) return EQF_E_BADARG;  // an output degree nothing feeds
-    a.B = {Wl[l3], 1, N, 0};
+    if (K == 0) return EQF_E_BADARG;  // an output segment nothing feeds
+    a.B = {Ws, 1, N, 0};
     a.C = {out + off, d3, Dout, N};
-    a.bias = (l3 == 0) ? bias0 : nullptr;
+    a.bias = (l3 == 0 && !odd) ? bias0 : nullptr;  // 0e only
     a.M = E * d3, a.N = N, a.K = K, a.accumulate = 0;
     a.vecA = 0;
-    a.vecB = aligned16(Wl[l3]) && N % 4 == 0;
+    a.vecB = aligned16(Ws) && N % 4 == 0;
     int rc = launch_rows<A_DTP, B_KN>(a, (hipStream_t)stream);
     if (rc) return rc;
     off += N * d3;
@@ -868,14 +870,15 @@ int eqf_dtp_linear_wgrad(const float* x, const float* coupling, const float* w, 
   const int Dout = irreps_dim(*out_irreps);
   int off = 0;
   for (int s = 0; s < out_irreps->nseg; ++s) {
-    const int l3 = out_irreps->l[s], N = out_irreps->mul[s], d3 = 2 * l3 + 1;
+    const int l3 = out_irreps->l[s], odd = out_irreps->odd[s] ? 1 : 0, N = out_irreps->mul[s], d3 = 2 * l3 + 1;
+    if (l3 > 3) return EQF_E_UNSUPPORTED;
     TnArgs a{};
-    const int K = build_dtp(paths, l3, x, coupling, w, a.dtp);
+    const int K = build_dtp(paths, l3, odd, x, coupling, w, a.dtp);
     if (K < 0) return K;
     if (K == 0) return EQF_E_BADARG;
     a.dtp.ept = BK / d3;
     a.B = {d_out + off, d3, Dout, N};
-    a.C = dWl[l3], a.ldc = N, a.M = K, a.N = N, a.R = E * d3;
+    a.C = dWl[seg_slot(l3, odd)], a.ldc = N, a.M = K, a.N = N, a.R = E * d3;
     a.rows_per_step = a.dtp.ept * d3;
     a.vecA = 0;
     a.vecB = aligned16(d_out + off) && Dout % 4 == 0 && N % 4 == 0;

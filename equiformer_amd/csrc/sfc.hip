@@ -289,7 +289,7 @@ __device__ __forceinline__ void f_block(const SfcFwdArgs& g, const int di, const
     if (i >= ntw) continue;
     const int c = ncol0 + boff[i] + r;
     float bvl = 0.f;
-    if (D.l3 == 0) {
+    if (D.sc) {
       if (c < D.N1) bvl = g.bias ? g.bias[c] : 0.f;
       else bvl = g.bias2 ? g.bias2[c - D.N1] : 0.f;
     }
@@ -1050,7 +1050,7 @@ int eqf_sfc_bwd_data(const float* x, const float* coupling, const float* w, cons
       int mt = 0;
       for (int d = 0; d < A.c.ndeg; ++d)
         for (int p = 0; p < P->npaths; ++p) {
-          if (P->in_off[p] != seg_off[s] || P->l3[p] != A.c.deg[d].l3) continue;
+          if (P->in_off[p] != seg_off[s] || !path_feeds(P, p, A.c.deg[d].l3, A.c.deg[d].odd)) continue;
           if (G.npath >= B_MAXPATH) return EQF_E_UNSUPPORTED;
           SfcBPath& Q = G.p[G.npath++];
           Q.deg = (short)d;

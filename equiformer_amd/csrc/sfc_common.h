@@ -22,11 +22,13 @@ struct SfcSlab {
 
 struct SfcDeg {
   const float* W;   // [K, N1] row-major: main consumer
-  const float* W2;  // [K, N2] row-major: second scalar consumer (degree 0 only), may be null
+  const float* W2;  // [K, N2] row-major: second scalar consumer (0e segment only), may be null
   float* dW;        // weight-gradient targets (same shapes), accumulated
   float* dW2;
   int l3, d3, K, N1, N2, Ncat;
-  int out1_off;    // offset of the degree segment inside an out1 row
+  int odd;         // parity of the segment: an E(3) row holds up to two segments of one degree
+  int sc;          // the 0e segment: the one that carries the bias and the second consumer (0o carries neither)
+  int out1_off;    // offset of the segment inside an out1 row
   int m_base, m_len;  // block of the coupling row holding the matrices of all paths into l3
   int slab0, nslab;
 };
@@ -93,7 +95,13 @@ __device__ __forceinline__ bool order_xy(const SfcOrder& o, int b, int& x, int& 
 }
 
 
-// Fill the degree / slab tables.  o1_irreps: one segment per output degree; n2 extra scalar columns on degree 0.
+// path p feeds the consumer segment (l, odd): same degree AND same parity
+inline bool path_feeds(const eqf_dtp_paths* P, int p, int l, int odd) {
+  return path_l3(*P, p) == l && path_odd(*P, p) == odd;
+}
+
+// Fill the segment ("degree") / slab tables.  o1_irreps: one segment per output irrep (l, parity); n2 extra scalar columns on
+// the 0e segment.  Wl / dWl: see seg_slot.
 inline int build_common(const float* x, const float* coupling, const float* w, const eqf_dtp_paths* P,
                  const float* const* Wl, const float* W2, float* const* dWl, float* dW2, float* o1,
                  const eqf_irreps* o1_irreps, float* o2, int n2, int E, SfcCommon& C) {
@@ -112,33 +120,35 @@ inline int build_common(const float* x, const float* coupling, const float* w, c
   for (int s = 0; s < o1_irreps->nseg; ++s) {
     SfcDeg& D = C.deg[s];
     D.l3 = o1_irreps->l[s], D.d3 = 2 * D.l3 + 1;
+    D.odd = o1_irreps->odd[s] ? 1 : 0;
+    D.sc = D.l3 == 0 && !D.odd;
     D.N1 = o1_irreps->mul[s];
-    D.N2 = (D.l3 == 0) ? n2 : 0;
-    have0 |= D.l3 == 0;
+    D.N2 = D.sc ? n2 : 0;
+    have0 |= D.sc != 0;
     D.Ncat = D.N1 + D.N2;
     D.out1_off = off;
     off += D.N1 * D.d3;
     if (D.l3 > 3 || D.Ncat % 32 != 0 || D.N1 % 32 != 0) return EQF_E_UNSUPPORTED;
-    D.W = Wl ? Wl[D.l3] : nullptr;
-    D.dW = dWl ? dWl[D.l3] : nullptr;
-    D.W2 = (D.l3 == 0) ? W2 : nullptr;
-    D.dW2 = (D.l3 == 0) ? dW2 : nullptr;
+    D.W = Wl ? Wl[seg_slot(D.l3, D.odd)] : nullptr;
+    D.dW = dWl ? dWl[seg_slot(D.l3, D.odd)] : nullptr;
+    D.W2 = D.sc ? W2 : nullptr;
+    D.dW2 = D.sc ? dW2 : nullptr;
     int K = 0, m_lo = 1 << 30, m_hi = 0;
     for (int p = 0; p < P->npaths; ++p)
-      if (P->l3[p] == D.l3) {
+      if (path_feeds(P, p, D.l3, D.odd)) {
         K = P->out_k[p];
         const int len = (2 * P->l1[p] + 1) * D.d3;
         if (P->m_off[p] < m_lo) m_lo = P->m_off[p];
         if (P->m_off[p] + len > m_hi) m_hi = P->m_off[p] + len;
       }
-    if (K == 0) return EQF_E_BADARG;  // an output degree nothing feeds
+    if (K == 0) return EQF_E_BADARG;  // an output segment nothing feeds
     if (K % 32 != 0) return EQF_E_UNSUPPORTED;
     D.K = K, D.m_base = m_lo, D.m_len = m_hi - m_lo;
     D.slab0 = nslab, D.nslab = K / 32;
     if (nslab + D.nslab > SFC_MAX_SLABS) return EQF_E_UNSUPPORTED;
     for (int q = 0; q < D.nslab; ++q) C.slab[nslab + q].d1 = 0;
     for (int p = 0; p < P->npaths; ++p) {
-      if (P->l3[p] != D.l3) continue;
+      if (!path_feeds(P, p, D.l3, D.odd)) continue;
       if (P->mul[p] % 32 != 0 || P->out_ch[p] % 32 != 0 || P->l1[p] > 3) return EQF_E_UNSUPPORTED;
       if (P->m_off[p] + 49 > 32767 || P->mul[p] > 32767) return EQF_E_UNSUPPORTED;
       for (int c = 0; c < P->mul[p]; c += 32) {

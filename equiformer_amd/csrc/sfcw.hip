@@ -54,6 +54,7 @@ struct WArgs {
   struct Deg {
     float *dW, *dW2;
     int d3, N1, N2, out1_off;
+    int sc;  // the 0e segment (bias gradient)
   } deg[SFC_MAX_DEG];
   WSlab slab[SFC_MAX_SLABS];
   WType type[W_MAXTYPE];
@@ -123,7 +124,7 @@ __device__ __forceinline__ void w_wave(const WArgs& g, const WType& T, const WSl
   const bool gated_seg = g.gate.on && S.g_off >= 0;  // uniform
   // bias gradients (degree 0 only): the workgroups that hold the FIRST slab of the degree cover every column once per edge
   // chunk; the owner of a tile sums the values it splits anyway
-  const bool do_bias = D3 == 1 && g.slab[T.slab0].sid == 0 && (g.db != nullptr || g.db2 != nullptr);
+  const bool do_bias = D3 == 1 && D.sc && g.slab[T.slab0].sid == 0 && (g.db != nullptr || g.db2 != nullptr);
   float bsum[KMAX];
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) bsum[k] = 0.f;
@@ -348,6 +349,7 @@ int plan_wgrad2(const SfcCommon& C, const eqf_dtp_paths* P, const XGate* gate, W
     if (D.d3 != 1 && D.d3 != 3 && D.d3 != 5) return EQF_E_UNSUPPORTED;
     if (D.nslab < 2) return EQF_E_UNSUPPORTED;  // (a lone slab would own all d_out tiles of its half-step: the one-wave kernel)
     A.deg[d].dW = D.dW, A.deg[d].dW2 = D.dW2, A.deg[d].d3 = D.d3, A.deg[d].N1 = D.N1, A.deg[d].N2 = D.N2;
+    A.deg[d].sc = D.sc;
     A.deg[d].out1_off = D.out1_off;
     const int ctm = x_ctmax(D.d3), cttot = D.Ncat / 32;
     const int ngc = eqf_cdiv(cttot, ctm), cps = eqf_cdiv(cttot, ngc);

@@ -217,7 +217,7 @@ inline SfcOrder xcd_order(int nx, int ny, int& nblocks) {
 
 // Gated input rows (the consumer side of Gate, nets/fast_activation.py:132-148): the operator's input x is NOT materialised;
 // the kernels read the gate's INPUT rows [scalars (S) | gates (G) | gated segments] and apply c_silu * silu to the scalar
-// segment and c_sig * sigmoid(gate of the channel) to the l > 0 segments where they load x, and the data gradient writes the
+// segment and c_sig * sigmoid(gate of the channel) to the gated segments (l > 0; 0o of an E(3) row) where they load x, and the data gradient writes the
 // gradient of those raw rows (the gate's backward, complete inside a 32-channel slab: every gate scalar belongs to one slab).
 struct XGate {
   int on, S, G;
@@ -234,7 +234,8 @@ inline int gate_map(const XGate& gt, const eqf_dtp_paths* P, int in_off, int mul
     g_off = -1;
     return 0;
   }
-  if (d1 == 1 || in_off < gt.S) return EQF_E_UNSUPPORTED;  // a second scalar segment / E(3) rows: not gated layouts
+  // every segment behind the S scalars is gated, channel by channel: l > 0 and, in E(3) rows, 0o (d1 == 1; only 0e is activated)
+  if (in_off < gt.S) return EQF_E_UNSUPPORTED;
   int before = 0, seen[EQF_MAX_SEG], ns = 0;
   for (int p = 0; p < P->npaths; ++p) {
     const int o = P->in_off[p];
@@ -338,6 +339,7 @@ struct XFwdArgs {
   SfcOrder ord;  // nx = edge tiles, ny = (degree, column group) items
   struct Deg {
     int d3, N1, Ncat, out1_off, cttot, nseg;
+    int sc;  // the 0e segment (bias, second consumer); a 0o segment has d3 == 1 too and carries neither
     long pf;
     XSeg seg[X_MAXSEG];
   } deg[SFC_MAX_DEG];
@@ -363,10 +365,11 @@ inline int plan_fwd(const SfcCommon& C, const eqf_dtp_paths* P, int mode, XFwdAr
     const SfcDeg& D = C.deg[d];
     XFwdArgs::Deg& X = A.deg[d];
     X.d3 = D.d3, X.N1 = D.N1, X.Ncat = D.Ncat, X.out1_off = D.out1_off, X.cttot = D.Ncat / 32, X.pf = pk[d].pf;
+    X.sc = D.sc;
     X.nseg = 0;
     // input segments in path (creation) order; the matrices of one segment's paths into this degree are contiguous
     for (int p = 0; p < P->npaths; ++p) {
-      if (P->l3[p] != D.l3) continue;
+      if (!path_feeds(P, p, D.l3, D.odd)) continue;
       int si = -1;
       for (int s = 0; s < X.nseg; ++s)
         if (X.seg[s].x_off == P->in_off[p]) si = s;
@@ -476,7 +479,7 @@ inline int plan_bwd(const SfcCommon& C, const eqf_dtp_paths* P, int mode, XBwdAr
       G.x_off = raw_off + c, G.g_off = g_off >= 0 ? g_off + c : g_off, G.mul = (short)mul, G.d1 = (short)d1, G.npath = 0;
       for (int d = 0; d < C.ndeg; ++d)
         for (int q = 0; q < P->npaths; ++q) {
-          if (P->in_off[q] != P->in_off[p] || P->l3[q] != C.deg[d].l3) continue;
+          if (P->in_off[q] != P->in_off[p] || !path_feeds(P, q, C.deg[d].l3, C.deg[d].odd)) continue;
           if (G.npath >= XB_MAXPATH) return EQF_E_UNSUPPORTED;
           XBPath& Q = G.p[G.npath++];
           Q.deg = (short)d, Q.mlen = (short)(d1 * C.deg[d].d3);

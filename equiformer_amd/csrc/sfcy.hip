@@ -432,7 +432,7 @@ __device__ __forceinline__ void yf_compute(const YFwdArgs& g, const YType& T, co
       const int c0 = (ct0 + ct) * 32;  // first column of the tile in the concatenated [main | second] output
       const bool main = c0 < D.N1;     // scalar: N1 % 32 == 0
       float bv = 0.f;
-      if (D3 == 1) bv = main ? (f.bias ? f.bias[c0 + r] : 0.f) : (f.bias2 ? f.bias2[c0 + r - D.N1] : 0.f);
+      if (D3 == 1 && D.sc) bv = main ? (f.bias ? f.bias[c0 + r] : 0.f) : (f.bias2 ? f.bias2[c0 + r - D.N1] : 0.f);
       asm volatile("" : "+v"(bv));  // (the bias has arrived: no wait inside the masked stores below)
       float* const base = main ? f.o1 + D.out1_off + c0 : f.o2 + (c0 - D.N1);  // uniform
       const unsigned ld = main ? f.ld1 : f.ld2;

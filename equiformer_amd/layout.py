@@ -136,12 +136,17 @@ class DtpTable:
         for i, p in enumerate(paths):
             for k in ("l1", "l2", "l3", "mul", "in_off", "out_off", "out_ch", "out_k", "w_off", "cg_off", "m_off"):
                 getattr(c, k)[i] = p[k]
+            if p["p3"] == -1:  # the parity of the output segment travels with its degree (include/equiformer_hip.h)
+                c.l3[i] |= lib.EQF_L3_ODD
         self.c = c
         self._cg_dev = {}
         self.key = (repr(self.layout_in.irreps), self.lmax_sh, repr(self.irreps_out))
-        # the DTP-generating GEMMs (eqf_dtp_linear_*, eqf_sfc_*) index their per-degree tables by l3: SE(3) models only
         self.has_odd = self.layout_in.has_odd or self.layout_out.has_odd
-        self.fusable = all(p["mul"] % 32 == 0 for p in paths) and not self.has_odd
+        # the DTP-generating GEMMs (eqf_dtp_linear_*, eqf_sfc_*) work on 32-channel slabs and match paths and consumer
+        # segments by (degree, parity): `seg_fusable` is their verdict for SE(3) and E(3) tables alike.  `fusable` keeps its
+        # first meaning -- fusable by degree alone, i.e. without odd segments.
+        self.seg_fusable = all(p["mul"] % 32 == 0 for p in paths)
+        self.fusable = self.seg_fusable and not self.has_odd
         # every input segment is read by at least one path (then the backward writes all of dx)
         self.in_covered = {p["in_off"] for p in paths} == set(self.layout_in.offsets)
 

@@ -14,6 +14,7 @@ if os.environ.get("EQF_LIB_VARIANT"):  # development A/B builds of the same sour
 
 EQF_MAX_SEG = 8
 EQF_MAX_PATHS = 72
+EQF_L3_ODD = 0x100  # eqf_dtp_paths.l3[p] of a path into an odd-parity output segment: degree | EQF_L3_ODD
 
 c_fp = ctypes.c_void_p  # device pointers travel as opaque addresses
 c_int = ctypes.c_int

@@ -399,8 +399,7 @@ class SeparableFCTP(nn.Module):
         self.lin = LinearRS(self.dtp.table.irreps_out, irreps_lin_output)
         self.norm = None
         self.gate = make_gate(self.irreps_node_output) if use_activation else None
-        self.fused_spec = (ops.DtpLinearSpec(self.dtp.table, self.lin.layout_out)
-                           if self.dtp.table.fusable and not self.lin.layout_out.has_odd else None)
+        self.fused_spec = ops.DtpLinearSpec.make(self.dtp.table, self.lin.layout_out)
         self.sfc_spec = ops.SfcSpec(self.dtp.table, self.lin.layout_out)
         if internal_weights:
             # row (path, channel) of the stacked lin weight -> index of its shared DTP weight
@@ -507,8 +506,7 @@ class GraphAttention(nn.Module):
             self.sep_value = SeparableFCTP(self.irreps_pre_attn, self.irreps_edge_attr, irreps_attn_heads,
                                            fc_neurons=None, use_activation=False, norm_layer=None,
                                            internal_weights=True)
-            self.alpha_fused_spec = (ops.DtpLinearSpec(self.sep_act.dtp.table, self.sep_alpha.layout_out)
-                                     if self.sep_act.dtp.table.fusable and not self.sep_alpha.layout_out.has_odd else None)
+            self.alpha_fused_spec = ops.DtpLinearSpec.make(self.sep_act.dtp.table, self.sep_alpha.layout_out)
             # value linear + attention-logit linear share ONE generation of the DTP output (concatenated degree-0
             # weight)
             self.act_sfc_spec = ops.SfcSpec(self.sep_act.dtp.table, self.sep_act.lin.layout_out, n2=mul_alpha)
@@ -521,7 +519,7 @@ class GraphAttention(nn.Module):
             irreps_attn_all = _simplified_sorted(irreps_alpha + irreps_attn_heads)
             self.sep = SeparableFCTP(self.irreps_pre_attn, self.irreps_edge_attr, irreps_attn_all, fc_neurons,
                                      use_activation=False, norm_layer=None, internal_weights=False)
-            n0 = sum(m for m, ir in irreps_attn_all if ir.l == 0)
+            n0 = sum(m for m, ir in irreps_attn_all if ir.l == 0 and ir.p == 1)
             hw = n0 // num_heads
             mah = self.mul_alpha_head
             self.register_buffer("_idx_alpha", torch.tensor([h * hw + k for h in range(num_heads) for k in range(mah)],
@@ -819,7 +817,7 @@ class EdgeDegreeEmbeddingNetwork(nn.Module):
         self.rad = RadialProfile(fc_neurons + [self.dw.tp.weight_numel])
         self.proj = LinearRS(self.dw.table.irreps_out, irreps_node_embedding)
         self.scale_scatter = ScaledScatter(avg_aggregate_num)
-        self.fused_spec = ops.DtpLinearSpec(self.dw.table, self.proj.layout_out) if self.dw.table.fusable else None
+        self.fused_spec = ops.DtpLinearSpec.make(self.dw.table, self.proj.layout_out)
         self.sfc_spec = ops.SfcSpec(self.dw.table, self.proj.layout_out)
         self.D = self.exp.layout_out.dim
         self.C = self.exp.layout_out.mul_of(0)

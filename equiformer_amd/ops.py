@@ -1873,26 +1873,35 @@ def dtp(x, coupling, w, table):
 
 
 class DtpLinearSpec:
-    """DTP output (degree l3, K(l3) channels) -> per-degree linear to `out_layout` (N(l3) channels).
-    Flat weight = [K(l3), N(l3)] blocks in ascending degree (e3nn LinearRS order on the simplified DTP irreps)."""
+    """DTP output (segment (l3, parity), K channels) -> per-segment linear to `out_layout` (N channels).
+    Flat weight = [K, N] blocks in segment order: ascending degree, even before odd (e3nn LinearRS order on the simplified
+    DTP irreps)."""
+
+    @classmethod
+    def make(cls, table, out_layout):
+        """the spec, or None where the DTP-generating GEMMs cannot serve the operator"""
+        if not table.seg_fusable:
+            return None
+        if (table.has_odd or out_layout.has_odd) and any(table.layout_out.seg_index(l, p) is None
+                                                          for (_, l), p in zip(out_layout.segs, out_layout.par)):
+            return None  # E(3): a consumer irrep no path reaches
+        return cls(table, out_layout)
 
     def __init__(self, table, out_layout):
         self.table, self.out_layout = table, out_layout
-        if table.has_odd or out_layout.has_odd:
-            raise NotImplementedError("the DTP-generating GEMMs index their tables by degree: SE(3) irreps only")
-        self.blocks = []  # (l3, K, N, w_off, mid_off, out_off)
+        self.blocks = []  # (l3, K, N, w_off, mid_off, out_off, slot): slot = index in the Wl / dWl pointer arrays
         w_off = 0
-        for (K, l3), mid_off in zip(table.layout_out.segs, table.layout_out.offsets):
-            j = out_layout.seg_index(l3)
+        for (K, l3), par, mid_off in zip(table.layout_out.segs, table.layout_out.par, table.layout_out.offsets):
+            j = out_layout.seg_index(l3, par)
             if j is None:
                 continue
             N = out_layout.segs[j][0]
-            self.blocks.append((l3, K, N, w_off, mid_off, out_layout.offsets[j]))
+            self.blocks.append((l3, K, N, w_off, mid_off, out_layout.offsets[j], _seg_slot(l3, par)))
             w_off += K * N
         self.weight_numel = w_off
-        if len(self.blocks) != len(out_layout.segs):
-            raise NotImplementedError("every output degree of a fused DTP-linear must be fed by the DTP")
-        self.bias_dim = out_layout.mul_of(0)
+        if len(self.blocks) != len(out_layout.segs) or any(l3 > 3 for (_, l3) in out_layout.segs):
+            raise NotImplementedError("every output segment of a fused DTP-linear must be fed by the DTP")
+        self.bias_dim = out_layout.mul_of(0)  # 0e
 
 
 class _DtpLinear(Function):
@@ -1907,8 +1916,8 @@ class _DtpLinear(Function):
         assert weight.numel() == spec.weight_numel
         out = torch.empty((E, spec.out_layout.dim), device=x.device, dtype=torch.float32)
         Wl = (ctypes.c_void_p * 8)()
-        for (l3, K, N, w_off, _, _) in spec.blocks:
-            Wl[l3] = weight.data_ptr() + 4 * w_off
+        for (l3, K, N, w_off, _, _, slot) in spec.blocks:
+            Wl[slot] = weight.data_ptr() + 4 * w_off
         call("eqf_dtp_linear_fwd", _p(x), _p(coupling), _p(w), spec.table.c_ref, Wl, _p(bias), _p(out),
              spec.out_layout.c_ref, E, _stream())
         ctx.save_for_backward(x, coupling, w, weight)
@@ -1932,7 +1941,7 @@ class _DtpLinear(Function):
         if need_mid:
             covered = len(spec.blocks) == len(table.layout_out.segs)
             dmid = (torch.empty if covered else torch.zeros)((E, Dmid), device=x.device, dtype=torch.float32)
-            for (l3, K, N, w_off, mid_off, out_off) in spec.blocks:
+            for (l3, K, N, w_off, mid_off, out_off, _) in spec.blocks:
                 d = 2 * l3 + 1
                 call("eqf_gemm_nt", _p(dout, out_off), rows(d, Dout, N), _p(weight, w_off), N, _p(dmid, mid_off),
                      rows(d, Dmid, K), None, E * d, K, N, 0, st)
@@ -1947,8 +1956,8 @@ class _DtpLinear(Function):
         if ctx.needs_input_grad[3]:
             dweight = dweight_
             dWl = (ctypes.c_void_p * 8)()
-            for (l3, K, N, w_off, _, _) in spec.blocks:
-                dWl[l3] = dweight.data_ptr() + 4 * w_off
+            for (l3, K, N, w_off, _, _, slot) in spec.blocks:
+                dWl[slot] = dweight.data_ptr() + 4 * w_off
             call("eqf_dtp_linear_wgrad", _p(x), _p(coupling), _p(w), table.c_ref, _p(dout), spec.out_layout.c_ref, dWl,
                  E, st)
         if want_b:
@@ -1964,47 +1973,51 @@ def dtp_linear(x, coupling, w, weight, bias, spec):
 
 # ------------------------------------------------------------------------------------------------- fused SeparableFCTP
 class SfcSpec:
-    """Fused DTP -> per-degree linear(s) (eqf_sfc_*): `out_layout` = irreps of the main consumer (one [K(l), N1(l)]
-    weight per degree), `n2` = width of an optional second scalar consumer fed by the degree-0 DTP output (its weight
-    is concatenated to the degree-0 matrix: [K(0), N1(0)+n2])."""
+    """Fused DTP -> per-segment linear(s) (eqf_sfc_*): `out_layout` = irreps of the main consumer (one [K, N1] weight per
+    segment (l, parity): one per degree in SE(3) rows, up to two in E(3) rows), `n2` = width of an optional second scalar
+    consumer fed by the 0e DTP output (its weight is concatenated to the 0e matrix: [K(0e), N1(0e)+n2]; 0o has neither a
+    second consumer nor a bias)."""
 
     def __init__(self, table, out_layout, n2=0):
         self.table, self.out_layout, self.n2 = table, out_layout, int(n2)
-        self.degs = []  # (l3, K, N1, Ncat)
-        self.w_offs = []  # offset of the [K, N1] block of each degree in the flat main weight
-        if table.has_odd or out_layout.has_odd:  # E(3) irreps: the un-fused tensor product + linear serve them
-            self.supported = False
-            return
-        ok = table.fusable
-        for (N1, l3) in out_layout.segs:
-            i = table.layout_out.seg_index(l3)
+        self.degs = []  # (l3, K, N1, Ncat) per consumer segment
+        self.pars = []  # parity (+1 / -1) of each entry of degs
+        self.w_offs = []  # offset of the [K, N1] block of each segment in the flat main weight
+        self._x_mask, self._packed_numel = {}, {}  # (filled on demand; present on an unsupported spec too: x_mask() == 0)
+        ok = table.seg_fusable
+        for (N1, l3), par in zip(out_layout.segs, out_layout.par):
+            i = table.layout_out.seg_index(l3, par)
             if i is None:
+                if table.has_odd or out_layout.has_odd:
+                    # E(3): a consumer irrep no path reaches (its output stays zero) -- the un-fused linear serves the operator
+                    self.supported = False
+                    return
                 raise NotImplementedError("output degree %d is not produced by the tensor product" % l3)
             K = table.layout_out.segs[i][0]
-            ncat = N1 + (self.n2 if l3 == 0 else 0)
+            ncat = N1 + (self.n2 if (l3 == 0 and par == 1) else 0)
             ok = ok and ncat % 32 == 0 and N1 % 32 == 0 and l3 <= 3
             self.degs.append((l3, K, N1, ncat))
+            self.pars.append(par)
             self.w_offs.append(sum(k * n for (_, k, n, _) in self.degs[:-1]))
         if self.n2 and out_layout.seg_index(0) is None:
             ok = False
         # LDS footprint of the forward workgroup (A tile + weight tile + coupling tile of 64 edges), see sfc.hip
-        for (l3, _, _, _) in self.degs:
-            m_len = sum((2 * p["l1"] + 1) * (2 * l3 + 1) for p in table.paths if p["l3"] == l3)
+        for (l3, _, _, _), par in zip(self.degs, self.pars):
+            m_len = sum((2 * p["l1"] + 1) * (2 * l3 + 1) for p in table.paths if (p["l3"], p["p3"]) == (l3, par))
             rows = 64 * (2 * l3 + 1)
             a_floats = max(32 * (rows + 1), rows * 36)  # [k][row] (fp32 MFMA step) / [row][k] (split-precision step)
             ok = ok and 4 * (a_floats + 32 * 68 + 64 * m_len) <= 160 * 1024
         self.supported = ok and len(self.degs) <= 4
         self.weight_numel = sum(k * n for (_, k, n, _) in self.degs)
-        k0 = [k for (l3, k, _, _) in self.degs if l3 == 0]
+        k0 = [k for (l3, k, _, _), par in zip(self.degs, self.pars) if l3 == 0 and par == 1]
         self.weight2_numel = (k0[0] * self.n2) if (self.n2 and k0) else 0
         self.bias_dim = out_layout.mul_of(0) + self.n2
-        used = {l3 for l3, _, _, _ in self.degs}
-        self.in_covered = {p["in_off"] for p in table.paths if p["l3"] in used} == set(table.layout_in.offsets)
+        used = {(l3, par) for (l3, _, _, _), par in zip(self.degs, self.pars)}
+        self.in_covered = ({p["in_off"] for p in table.paths if (p["l3"], p["p3"]) in used}
+                           == set(table.layout_in.offsets))
         # split-precision kernels (csrc/sfcx.hip): each of the three launches has its own table limits (input slabs, work
         # items, LDS); the planners themselves are asked once per mode (eqf_sfcx_supported, host only) and a launch they
         # reject is served by the exact-fp32 kernel of the same shape
-        self._x_mask = {}
-        self._packed_numel = {}
 
     def x_mask(self, mode, E=None):
         """bit 0 forward, bit 1 data gradient, bit 2 weight gradient of csrc/sfcx.hip can serve this operator in `mode`.
@@ -2041,10 +2054,17 @@ class SfcSpec:
         return n
 
 
+def _seg_slot(l3, par):
+    """index of the segment (l3, parity) in the Wl / dWl pointer arrays of the DTP-generating GEMMs: even segments at l3 (an
+    SE(3) operator indexes by degree), odd ones at 4 + l3 (include/equiformer_hip.h, EQF_L3_ODD)"""
+    return l3 if par == 1 else 4 + l3
+
+
 def _ptr_array(pairs):
+    """pairs: (slot, address), slot = _seg_slot(l3, parity) -- the plain degree for even segments"""
     arr = (ctypes.c_void_p * 8)()
-    for l3, addr in pairs:
-        arr[l3] = addr
+    for slot, addr in pairs:
+        arr[slot] = addr
     return arr
 
 
@@ -2082,7 +2102,8 @@ def _sfc_mode(spec, E=None):
 
 
 def _sfc_Wl(weight, spec):
-    return _ptr_array((l3, weight.data_ptr() + 4 * off) for (l3, _, _, _), off in zip(spec.degs, spec.w_offs))
+    return _ptr_array((_seg_slot(l3, par), weight.data_ptr() + 4 * off)
+                      for (l3, _, _, _), par, off in zip(spec.degs, spec.pars, spec.w_offs))
 
 
 def _sfc_pack(weight, weight2, spec, mode):
@@ -2134,7 +2155,7 @@ def _sfc_bwd_weight(x, coupling, w, d1, d2, spec, dweight, dweight2, mode=None, 
         call("eqf_sfc_bwd_weight", _p(x), _p(coupling), _p(w), spec.table.c_ref, _p(d1), spec.out_layout.c_ref, _p(d2),
              spec.n2, dWl, _p(dweight2), x.shape[0], _stream())
         return False
-    if (dbias is not None or dbias2 is not None) and 0 in [l3 for l3, _, _, _ in spec.degs]:
+    if (dbias is not None or dbias2 is not None) and spec.out_layout.seg_index(0) is not None:  # a 0e segment
         call("eqf_sfcx_bwd_weight_bias", _p(x), _p(coupling), _p(w), spec.table.c_ref, _p(d1), spec.out_layout.c_ref, _p(d2),
              spec.n2, dWl, _p(dweight2), _p(dbias), _p(dbias2), x.shape[0], mode, _stream())
         return True
@@ -2423,6 +2444,9 @@ def sep_fctp_gated_ok(spec, x_raw_dim, S, gated_layout, E=None):
     if max([p["l1"] for p in spec.table.paths] + [l3 for l3, _, _, _ in spec.degs]) > 2:
         return False
     li = spec.table.layout_in
+    if spec.table.has_odd and not (li.par[0] == 1 and li.segs[1:] == gated_layout.segs and li.par[1:] == gated_layout.par
+                                   and spec.in_covered):
+        return False  # E(3): the S scalars are 0e, every other segment (0o included) is a gated one
     return li.segs[0] == (S, 0) and S % 32 == 0 and li.dim == S + gated_layout.dim
 
 

@@ -33,6 +33,12 @@ extern "C" {
 #define EQF_MAX_SEG 8
 #define EQF_MAX_PATHS 72
 
+/* eqf_dtp_paths.l3[p] of a path whose output irrep has ODD parity carries this flag beside the degree (E(3) tables; the
+ * tables of SE(3) models hold plain degrees).  The DTP-generating GEMMs match a consumer segment (l, odd) of their output
+ * irreps with the paths of exactly that (l3, parity); their host arrays of per-segment pointers (Wl, dWl: 8 entries) hold
+ * the even segment of degree l at index l and the odd one at index 4 + l. */
+#define EQF_L3_ODD 0x100
+
 #define EQF_E_BADARG (-1)
 #define EQF_E_UNSUPPORTED (-2)
 
@@ -47,7 +53,8 @@ typedef struct eqf_irreps {
 /* Depth-wise tensor product ('uvu', mul2 == 1) path table.  Path p couples input segment of degree
  * l1[p] (row offset in_off[p], multiplicity mul[p]) with the spherical harmonic of degree l2[p] into
  * output degree l3[p]; its mul[p] output channels start at channel out_ch[p] of the output segment
- * (row offset out_off[p], total channels out_k[p]); its per-edge weights start at w_off[p].
+ * (row offset out_off[p], total channels out_k[p]); its per-edge weights start at w_off[p].  l3[p] of a path into an
+ * odd-parity segment is  degree | EQF_L3_ODD.
  * cg_off[p] indexes the dense table  cg[cg_off + (i*(2*l2+1) + j)*(2*l3+1) + k]  which already
  * includes the sqrt(2*l3+1) path normalisation.                     [ref: e3nn o3.TensorProduct codegen] */
 typedef struct eqf_dtp_paths {
