@@ -10,8 +10,8 @@ from torch import nn
 from .. import ops
 from ..graph import EdgeGraph
 from ..irreps import Irreps
-from .layers import (Activation, EdgeContext, EdgeDegreeEmbeddingNetwork, EquivariantLayerNormV2,  # noqa: F401
-                     FeedForwardNetwork, FullyConnectedTensorProductRescale, GaussianRadialBasisLayer, GraphAttention,
+from .layers import (Activation, EdgeContext, EdgeDegreeEmbeddingNetwork, EquivariantGraphNorm,  # noqa: F401
+                     EquivariantInstanceNorm, EquivariantLayerNormV2, FeedForwardNetwork, FullyConnectedTensorProductRescale, GaussianRadialBasisLayer, GraphAttention,
                      LinearRS, NodeEmbeddingNetwork, RadialBank, RadialBasis, ScaledScatter, SeparableFCTP, TransBlock, get_norm_layer)
 from .registry import register_model
 
@@ -99,7 +99,8 @@ class _Trunk(nn.Module):
         no_wd_list = []
         named = {name for name, _ in self.named_parameters()}
         for module_name, module in self.named_modules():
-            if isinstance(module, (nn.Linear, nn.LayerNorm, EquivariantLayerNormV2, GaussianRadialBasisLayer, RadialBasis)):
+            if isinstance(module, (nn.Linear, nn.LayerNorm, EquivariantLayerNormV2, EquivariantInstanceNorm, EquivariantGraphNorm,
+                                   GaussianRadialBasisLayer, RadialBasis)):
                 for parameter_name, _ in module.named_parameters():
                     if isinstance(module, nn.Linear) and "weight" in parameter_name:
                         continue
@@ -160,7 +161,7 @@ class _Trunk(nn.Module):
             b = b + extra
         for blk in self.blocks:
             a, b = blk.forward_pair(a, b, node_attr=None, ectx=ectx)
-        _, node_features = self.norm.forward_sum(a, b)
+        _, node_features = self.norm.forward_sum(a, b, graph=graph)
         return node_features, ectx
 
 

@@ -6,6 +6,9 @@ Reference sources of the semantics (paths relative to the reference root):
   nets/tensor_product_rescale.py:15-174   TensorProductRescale / FullyConnectedTensorProductRescale / LinearRS
   nets/fast_activation.py:15-160          Activation / Gate
   nets/layer_norm.py:62-152               EquivariantLayerNormV2
+  nets/graph_norm.py:9-134                EquivariantGraphNorm
+  nets/instance_norm.py:9-134             EquivariantInstanceNorm
+  nets/fast_layer_norm.py                 EquivariantLayerNormFast
   nets/radial_func.py:9-49                RadialProfile
   nets/gaussian_rbf.py:13-40              GaussianRadialBasisLayer
   nets/graph_attention_transformer.py     DepthwiseTensorProduct :157, SeparableFCTP :186, GraphAttention :403,
@@ -168,31 +171,120 @@ class EquivariantLayerNormV2(nn.Module):
         self.affine_weight = nn.Parameter(torch.ones(self.irreps.num_irreps))
         self.affine_bias = nn.Parameter(torch.zeros(sum(m for m, ir in self.irreps if ir.l == 0 and ir.p == 1)))
 
-    def forward(self, node_input, **kwargs):
-        if node_input.shape[-1] != self.layout.dim:
-            raise AssertionError("`ix` should have reached node_input.size(-1) ({}), but it ended at {}".format(
-                node_input.shape[-1], self.layout.dim))
+    def forward(self, node_input, graph=None, **kwargs):
+        _check_row(node_input, self.layout)
         return ops.layer_norm(node_input, self.affine_weight, self.affine_bias, self.layout, self.eps)
 
-    def forward_sum(self, a, b):
-        """(a + b, norm(a + b)) in one launch: the residual add that precedes every norm of the transformer."""
-        if a.shape[-1] != self.layout.dim:
-            raise AssertionError("`ix` should have reached node_input.size(-1) ({}), but it ended at {}".format(
-                a.shape[-1], self.layout.dim))
+    def forward_sum(self, a, b, graph=None):
+        """(a + b, norm(a + b)) in one launch: the residual add that precedes every norm of the transformer.  `graph` (what
+        the per-graph norms below need) is accepted and ignored."""
+        _check_row(a, self.layout)
         return ops.add_layer_norm(a, b, self.affine_weight, self.affine_bias, self.layout, self.eps)
 
     def __repr__(self):
         return "{}({}, eps={})".format(self.__class__.__name__, self.irreps, self.eps)
 
 
+def _check_row(x, layout):
+    if x.shape[-1] != layout.dim:
+        raise AssertionError("`ix` should have reached node_input.size(-1) ({}), but it ended at {}".format(
+            x.shape[-1], layout.dim))
+
+
+class EquivariantLayerNormFast(nn.Module):
+    """[ref: nets/fast_layer_norm.py] the reference's second formulation of the layer norm: the same function of the same
+    parameters as EquivariantLayerNormV2 (2e-15 apart in fp64), so it runs on the same kernels.  A class of its own, NOT a
+    subclass of V2: the reference's no_weight_decay() does not list it, and the mirror here must not either."""
+
+    def __init__(self, irreps, eps=1e-5, affine=True, normalization="component"):
+        super().__init__()
+        if not affine or normalization != "component":
+            raise NotImplementedError("EquivariantLayerNormFast: only affine=True, normalization='component' is built")
+        self.irreps = Irreps(irreps)
+        self.layout = RowLayout(self.irreps.simplify())
+        self.eps = eps
+        self.affine_weight = nn.Parameter(torch.ones(self.irreps.num_irreps))
+        self.affine_bias = nn.Parameter(torch.zeros(sum(m for m, ir in self.irreps if ir.l == 0 and ir.p == 1)))
+
+    def forward(self, node_input, graph=None, **kwargs):
+        _check_row(node_input, self.layout)
+        return ops.layer_norm(node_input, self.affine_weight, self.affine_bias, self.layout, self.eps)
+
+    def forward_sum(self, a, b, graph=None):
+        _check_row(a, self.layout)
+        return ops.add_layer_norm(a, b, self.affine_weight, self.affine_bias, self.layout, self.eps)
+
+    def __repr__(self):
+        return "{}({}, eps={})".format(self.__class__.__name__, self.irreps, self.eps)
+
+
+class _PerGraphNorm(nn.Module):
+    """What EquivariantGraphNorm and EquivariantInstanceNorm share: statistics per (graph, channel) over the nodes of a graph
+    (ops.graph_norm; csrc/graphnorm.hip).  Only the defaults every model uses are built."""
+
+    def __init__(self, irreps, eps=1e-5, affine=True, reduce="mean", normalization="component"):
+        super().__init__()
+        assert isinstance(reduce, str), "reduce should be passed as a string value"
+        assert reduce in ["mean", "max"], "reduce needs to be 'mean' or 'max'"
+        assert normalization in ["norm", "component"], "normalization needs to be 'norm' or 'component'"
+        if not affine or reduce != "mean" or normalization != "component":
+            raise NotImplementedError("{}: only affine=True, reduce='mean', normalization='component' is built (got "
+                                      "affine={}, reduce={!r}, normalization={!r})".format(
+                                          self.__class__.__name__, affine, reduce, normalization))
+        self.irreps = Irreps(irreps)
+        self.layout = RowLayout(self.irreps.simplify())
+        self.eps, self.affine, self.reduce, self.normalization = eps, affine, reduce, normalization
+        self._register(self.irreps.num_irreps, sum(m for m, ir in self.irreps if ir.l == 0 and ir.p == 1))
+
+    def _mean_shift(self):
+        return None  # the instance norm has no such parameter (= 1)
+
+    def forward(self, node_input, graph=None, **kwargs):
+        _check_row(node_input, self.layout)
+        return ops.graph_norm(node_input, self._mean_shift(), self.affine_weight, self.affine_bias, self.layout, graph,
+                              self.eps)
+
+    def forward_sum(self, a, b, graph=None):
+        """(a + b, norm(a + b)): the residual add rides on the norm's kernels."""
+        _check_row(a, self.layout)
+        return ops.add_graph_norm(a, b, self._mean_shift(), self.affine_weight, self.affine_bias, self.layout, graph,
+                                  self.eps)
+
+    def __repr__(self):
+        return "{} ({}, eps={})".format(self.__class__.__name__, self.irreps, self.eps)
+
+
+class EquivariantGraphNorm(_PerGraphNorm):
+    """[ref: nets/graph_norm.py:9-134] parameters in the reference's order: mean_shift, affine_weight, affine_bias."""
+
+    def _register(self, num_features, num_scalar):
+        self.mean_shift = nn.Parameter(torch.ones(num_scalar))
+        self.affine_weight = nn.Parameter(torch.ones(num_features))
+        self.affine_bias = nn.Parameter(torch.zeros(num_scalar))
+
+    def _mean_shift(self):
+        return self.mean_shift
+
+
+class EquivariantInstanceNorm(_PerGraphNorm):
+    """[ref: nets/instance_norm.py:9-134] the graph norm without the mean shift."""
+
+    def _register(self, num_features, num_scalar):
+        self.affine_weight = nn.Parameter(torch.ones(num_features))
+        self.affine_bias = nn.Parameter(torch.zeros(num_scalar))
+
+
 def get_norm_layer(norm_type):
+    if norm_type == "graph":
+        return EquivariantGraphNorm
+    if norm_type == "instance":
+        return EquivariantInstanceNorm
     if norm_type == "layer":
         return EquivariantLayerNormV2
+    if norm_type == "fast_layer":
+        return EquivariantLayerNormFast
     if norm_type is None:
         return None
-    if norm_type in ("graph", "instance", "fast_layer"):
-        raise NotImplementedError("norm type {!r} is outside the MI355X hot path (every registered model uses "
-                                  "'layer')".format(norm_type))
     raise ValueError("Norm type {} not supported.".format(norm_type))
 
 
@@ -749,8 +841,9 @@ class TransBlock(nn.Module):
         return x if self.drop_path is None else self.drop_path(x, ectx.graph)
 
     def forward(self, node_input, node_attr=None, ectx=None, **kwargs):
-        node_output = node_input + self._drop(self.attention(self.norm_1(node_input), ectx=ectx), ectx)
-        node_features = self._drop(self.ffn(self.norm_2(node_output), node_attr), ectx)
+        graph = ectx.graph
+        node_output = node_input + self._drop(self.attention(self.norm_1(node_input, graph=graph), ectx=ectx), ectx)
+        node_features = self._drop(self.ffn(self.norm_2(node_output, graph=graph), node_attr), ectx)
         if self.ffn_shortcut is not None:
             node_output = self.ffn_shortcut(node_output, node_attr)
         return node_output + node_features
@@ -759,8 +852,9 @@ class TransBlock(nn.Module):
         """The same block on a lazily summed input node_input = a + b, returning its output as a lazy pair as well
         (node_output, node_features): every residual add then rides on the layer norm that follows it (norm_1 here,
         norm_2, and the next block's norm_1 or the model's final norm) instead of being its own launch."""
-        node_input, h = self.norm_1.forward_sum(a, b)
-        node_output, h2 = self.norm_2.forward_sum(node_input, self._drop(self.attention(h, ectx=ectx), ectx))
+        node_input, h = self.norm_1.forward_sum(a, b, graph=ectx.graph)
+        node_output, h2 = self.norm_2.forward_sum(node_input, self._drop(self.attention(h, ectx=ectx), ectx),
+                                                  graph=ectx.graph)
         node_features = self._drop(self.ffn(h2, node_attr), ectx)
         if self.ffn_shortcut is not None:
             node_output = self.ffn_shortcut(node_output, node_attr)

@@ -352,6 +352,106 @@ def add_layer_norm(a, b, weight, bias, layout, eps=1e-5):
     return _AddLayerNorm.apply(a, b, weight, bias, layout, eps)
 
 
+# ------------------------------------------------------------------------------------------------- graph / instance norm
+def _gn_graph(graph, n):
+    """(mol_ptr, batch, num_graphs) of the EdgeGraph whose nodes are the rows: the statistics of these norms are taken per
+    (graph, channel) over the nodes of a graph."""
+    if graph is None or getattr(graph, "batch", None) is None or getattr(graph, "mol_ptr", None) is None:
+        raise ValueError("the graph / instance norm needs the batch's EdgeGraph (graph=...) with batch and mol_ptr")
+    if graph.batch.shape[0] != n or graph.num_graphs <= 0:
+        raise ValueError("graph norm: %d rows, but the graph has %d nodes in %d graphs"
+                         % (n, graph.batch.shape[0], graph.num_graphs))
+    _chk(graph.mol_ptr, graph.batch)
+    return graph.mol_ptr, graph.batch, int(graph.num_graphs)
+
+
+def _gn_fwd(a, b, mean_shift, weight, bias, layout, graph, eps):
+    _chk(a, b, mean_shift, weight, bias)
+    n = a.shape[0]
+    mol_ptr, batch, B = _gn_graph(graph, n)
+    s = torch.empty_like(a) if b is not None else None
+    y = torch.empty_like(a)
+    mean = torch.empty((B, bias.numel()), device=a.device, dtype=torch.float32)
+    rstd = torch.empty((B, weight.numel()), device=a.device, dtype=torch.float32)
+    call("eqf_graphnorm_fwd", _p(a), _p(b), _p(s), _p(mean_shift), _p(weight), _p(bias), _p(y), _p(mean), _p(rstd),
+         _p(mol_ptr), _p(batch), n, B, layout.c_ref, float(eps), _stream())
+    return s, y, mean, rstd
+
+
+def _gn_bwd(x, mean_shift, weight, dy, dres, mean, rstd, graph, layout, nb, want):
+    """(dx, d_mean_shift, d_weight, d_bias): first order, eqf_graphnorm_bwd; the per-graph partials go through a workspace
+    of this call's."""
+    dy = _c(dy)
+    dres = _c(dres) if dres is not None else None
+    _chk(dy, dres)
+    mol_ptr, batch, B = _gn_graph(graph, x.shape[0])
+    dx = torch.empty_like(x)
+    ws = torch.empty(max(1, B * (weight.numel() + 3 * nb)), device=x.device, dtype=torch.float64)
+    dw, db = _zeros2(weight.numel(), nb, x.device) if want else (None, None)
+    dms = _zeros(nb, x.device) if (want and mean_shift is not None) else None
+    call("eqf_graphnorm_bwd", _p(x), _p(mean_shift), _p(weight), _p(dy), _p(dres), _p(mean), _p(rstd), _p(mol_ptr),
+         _p(batch), _p(dx), _p(dw), _p(db), _p(dms), ctypes.c_void_p(ws.data_ptr()), x.shape[0], B, layout.c_ref, _stream())
+    return dx, dms, dw, db
+
+
+class _GraphNorm(Function):
+    """EquivariantGraphNorm (mean_shift given) / EquivariantInstanceNorm (mean_shift None).  Second order is not built: a
+    backward that runs with grad enabled (a force pass under create_graph) computes the first-order result with the same
+    kernels and hands it out guarded -- force evaluation works, differentiating the forces raises."""
+
+    @staticmethod
+    def forward(ctx, x, mean_shift, weight, bias, layout, graph, eps):
+        x = _c(x)
+        _, y, mean, rstd = _gn_fwd(x, None, mean_shift, weight, bias, layout, graph, eps)
+        ctx.save_for_backward(x, mean_shift, weight, mean, rstd)
+        ctx.layout, ctx.graph, ctx.nb = layout, graph, bias.numel()
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean_shift, weight, mean, rstd = ctx.saved_tensors
+        dx, dms, dw, db = _gn_bwd(x, mean_shift, weight, dy, None, mean, rstd, ctx.graph, ctx.layout, ctx.nb,
+                                  _want_param_grads())
+        if torch.is_grad_enabled():
+            dx, dms, dw, db = (_guard(t, dy, "graph norm") for t in (dx, dms, dw, db))
+        return dx, dms, dw, db, None, None, None
+
+
+def graph_norm(x, mean_shift, weight, bias, layout, graph, eps=1e-5):
+    """Graph norm of the rows x over the nodes of each graph of `graph`; mean_shift None: instance norm."""
+    return _GraphNorm.apply(x, mean_shift, weight, bias, layout, graph, eps)
+
+
+class _AddGraphNorm(Function):
+    """(s, y) = (a + b, norm(a + b)) for the graph / instance norm: the residual add rides on the statistics and apply
+    kernels, and the backward folds the gradient arriving at s into the norm's input gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, mean_shift, weight, bias, layout, graph, eps):
+        a, b = _c(a), _c(b)
+        s, y, mean, rstd = _gn_fwd(a, b, mean_shift, weight, bias, layout, graph, eps)
+        ctx.save_for_backward(s, mean_shift, weight, mean, rstd)
+        ctx.layout, ctx.graph, ctx.nb = layout, graph, bias.numel()
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        s, mean_shift, weight, mean, rstd = ctx.saved_tensors
+        if dy is None:  # the normalised branch is unused: identity on the sum
+            return ds, ds, None, None, None, None, None, None
+        d, dms, dw, db = _gn_bwd(s, mean_shift, weight, dy, ds, mean, rstd, ctx.graph, ctx.layout, ctx.nb,
+                                 _want_param_grads())
+        if torch.is_grad_enabled():
+            dep = dy if (ds is None or dy.requires_grad) else ds
+            d, dms, dw, db = (_guard(t, dep, "graph norm") for t in (d, dms, dw, db))
+        return d, d, dms, dw, db, None, None, None
+
+
+def add_graph_norm(a, b, mean_shift, weight, bias, layout, graph, eps=1e-5):
+    """(a + b, graph_norm(a + b)); mean_shift None: instance norm."""
+    return _AddGraphNorm.apply(a, b, mean_shift, weight, bias, layout, graph, eps)
+
+
 # ------------------------------------------------------------------------------------------------- per-degree linear
 class LinearSpec:
     """Pairs (degree-wise GEMMs) of a LinearRS / FCTP-with-scalar-attr between two row layouts.

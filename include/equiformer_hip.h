@@ -389,6 +389,30 @@ int eqf_add_layernorm_bwd(const float* x, const float* weight, const float* dy, 
                           const float* mean0, float* dx, float* d_weight, float* d_bias, int rows,
                           const eqf_irreps* irreps, void* stream);
 
+/* EquivariantGraphNorm / EquivariantInstanceNorm (reduce='mean', 'component' normalisation, affine): the statistics are
+ * taken per (graph, channel) over the nodes of a graph, not per row.  For a channel u of a segment of dimension d in a
+ * graph of n nodes: 0e segments c = x - mean_shift[u] * mean_nodes(x), all others (0o included) c = x;
+ * y = c * (sum_nodes sum_m c^2 / (n d) + eps)^(-1/2) * weight[u] (+ bias[u] on 0e).  mean_shift == NULL is the instance
+ * norm (mean_shift == 1, no such parameter).  [ref: nets/graph_norm.py:9-134, nets/instance_norm.py:9-134]
+ * Rows are sorted by graph: mol_ptr[num_graphs + 1] bounds the rows of a graph, batch[rows] names the graph of a row (a row
+ * whose batch entry is outside [0, num_graphs) gets y = 0); a graph without rows is legal.  x2 / xsum optional as in
+ * eqf_add_layernorm_fwd.  Outputs besides y: mean [num_graphs, C0] (C0 = number of 0e channels) and rstd
+ * [num_graphs, num_irreps], inputs of bwd.  No atomics: results do not depend on launch order.  num_graphs <= 0 is an
+ * argument error. */
+int eqf_graphnorm_fwd(const float* x, const float* x2, float* xsum, const float* mean_shift, const float* weight,
+                      const float* bias, float* y, float* mean, float* rstd, const int* mol_ptr, const int* batch, int rows,
+                      int num_graphs, const eqf_irreps* irreps, float eps, void* stream);
+/* dx = norm'(dy) + dres (dres may be NULL); `x` is the normalised input (xsum of the forward).  d_weight[num_irreps],
+ * d_bias[C0], d_mean_shift[C0] ACCUMULATED, each element by one thread from per-graph partials summed in graph order
+ * (d_weight and d_bias may be NULL together: no parameter gradients; d_mean_shift NULL for the instance norm).
+ * workspace: num_graphs * (num_irreps + 3 * C0) DOUBLES of the caller's, overwritten (the per-graph partials, kept in
+ * fp64: in graphs of one to three nodes dx is a small difference of them).
+ * [ref: the backward of nets/graph_norm.py:57-134, nets/instance_norm.py:56-134] */
+int eqf_graphnorm_bwd(const float* x, const float* mean_shift, const float* weight, const float* dy, const float* dres,
+                      const float* mean, const float* rstd, const int* mol_ptr, const int* batch, float* dx,
+                      float* d_weight, float* d_bias, float* d_mean_shift, double* workspace, int rows, int num_graphs,
+                      const eqf_irreps* irreps, void* stream);
+
 /* Gate: in = [scalars(S) | gates(G) | gated segments], out = [c_silu*silu(scalars) | gated * c_sig*sigmoid(gates)].
  * `gated` lists the l>0 segments (sum of mul = G).  in rows have S+G+dim(gated) floats, out rows S+dim(gated).
  * [ref: nets/fast_activation.py:132-148] */
