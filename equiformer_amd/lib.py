@@ -50,6 +50,7 @@ _P_IRR = ctypes.POINTER(EqfIrreps)
 _P_PATHS = ctypes.POINTER(EqfDtpPaths)
 _PP = ctypes.POINTER(ctypes.c_void_p)
 _f = ctypes.c_float
+_d = ctypes.c_double
 _u64 = ctypes.c_ulonglong
 _long = ctypes.c_long
 
@@ -152,6 +153,10 @@ SIGNATURES = {
                               c_fp, c_fp],
     "eqf_rbf_bessel_bwd2": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, _f, c_fp, c_fp, c_fp, c_fp],
     "eqf_edge_geom_bwd2": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
+    "eqf_dens_corrupt": [c_fp, c_fp, c_fp, c_int, _f, _f, _f, _u64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "eqf_dens_loss_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, _d, _d, _d, c_fp, c_fp, c_fp],
+    "eqf_dens_loss_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, _d, _d, _d, c_fp, c_fp,
+                          c_fp],
     "eqf_prof_enable": [ctypes.c_char_p],
     "eqf_prof_report": [ctypes.c_char_p, c_int],
 }

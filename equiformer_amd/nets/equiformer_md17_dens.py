@@ -65,10 +65,14 @@ class Equiformer_MD17_DeNS(GraphAttentionTransformerMD17):
         return [self.denoising_pos_head]
 
     @torch.enable_grad()
-    def forward(self, data):
+    def forward(self, data, graph=None):
+        """graph: (extension of the reference signature, as GraphAttentionTransformerMD17.forward has it) the radius graph of
+        `data.pos` -- the CORRUPTED positions --, built by the caller: what a captured train step passes
+        (equiformer_amd/dens.py; the graph's edge count is read back on the host, outside the capture)."""
         node_atom, batch = data.z, data.batch
         pos = data.pos.to(torch.float32).contiguous().requires_grad_(True)
-        graph = EdgeGraph.from_radius(pos, batch, self.max_radius, max_num_neighbors=1000)
+        if graph is None:
+            graph = EdgeGraph.from_radius(pos, batch, self.max_radius, max_num_neighbors=1000)
         atom_embedding, _, _ = self.atom_embed(node_atom)
         n = pos.shape[0]
         if hasattr(data, "force") and self.use_force_encoding:  # [ref: :276-289]

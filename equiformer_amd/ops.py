@@ -1645,6 +1645,94 @@ def vec_sh(vec, keep, lmax, norm_scale):
     return out
 
 
+def _mask_u8(mask, rows):
+    """A [rows] bool / uint8 device mask as the one-byte-per-row buffer the kernels read (a view, no launch)."""
+    if not mask.is_cuda:
+        raise HipOnlyError("mask on %s" % mask.device)
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise HipOnlyError("masks are bool / uint8, got %s" % mask.dtype)
+    if mask.numel() != rows:
+        raise ValueError("mask has %d entries, the batch has %d rows" % (mask.numel(), rows))
+    return _c(mask).view(torch.uint8)
+
+
+def dens_corrupt(pos, dy, batch, std, prob, corrupt_ratio=None, seed=0):
+    """(pos_out, force, noise_vec, noise_mask, denoising_pos_mask) of the DeNS corruption, one launch, no gradient
+    [ref: main_md17_dens.py:514-548]: pos [N, 3], dy [N, 3] fp32, batch [N] int32; the masks come back as bool.  Every random
+    number is a function of (seed, index) alone: the same seed gives the same bits."""
+    pos, dy, batch = _c(pos.detach()), _c(dy.detach()), _c(batch)
+    _chk(pos, dy, batch)
+    if batch.dtype != torch.int32:
+        raise HipOnlyError("kernels take int32 indices, got %s" % batch.dtype)
+    N = pos.shape[0]
+    if tuple(pos.shape) != (N, 3) or tuple(dy.shape) != (N, 3) or batch.numel() != N:
+        raise ValueError("dens_corrupt: pos %s, dy %s, batch %s" % (tuple(pos.shape), tuple(dy.shape), tuple(batch.shape)))
+    pos_out, force, noise_vec = torch.empty_like(pos), torch.empty_like(pos), torch.empty_like(pos)
+    noise_mask = torch.empty(N, dtype=torch.bool, device=pos.device)
+    denoising_pos_mask = torch.empty(N, dtype=torch.bool, device=pos.device)
+    call("eqf_dens_corrupt", _p(pos), _p(dy), _p(batch), N, float(std), float(prob),
+         -1.0 if corrupt_ratio is None else float(corrupt_ratio), int(seed) & (2 ** 64 - 1), _p(pos_out), _p(force),
+         _p(noise_vec), ctypes.c_void_p(noise_mask.data_ptr()), ctypes.c_void_p(denoising_pos_mask.data_ptr()), _stream())
+    return pos_out, force, noise_vec, noise_mask, denoising_pos_mask
+
+
+class _DensLoss(Function):
+    """First order only: pred_dy carries the second-order graph of the forces, the loss does not."""
+
+    @staticmethod
+    def forward(ctx, pred_y, pred_dy, y, dy, noise_vec, noise_mask, row_mask, weights, stats, task_mean, task_std, noise_std):
+        pred_y, pred_dy, y = _c(pred_y), _c(pred_dy), _c(y)
+        loss = torch.empty((), device=pred_y.device, dtype=torch.float32)
+        ctx.consts = (pred_dy.shape[0], pred_y.numel(), float(task_mean), float(task_std), float(noise_std))
+        N, nB, mean, std, nstd = ctx.consts
+        call("eqf_dens_loss_fwd", _p(pred_y), _p(y), _p(pred_dy), _p(dy), _p(noise_vec),
+             ctypes.c_void_p(_nonnull(noise_mask)), _p(row_mask), _p(weights), N, nB, mean, std, nstd, _p(loss), _p(stats),
+             _stream())
+        ctx.save_for_backward(pred_y, pred_dy, y, dy, noise_vec, noise_mask, row_mask, weights, stats)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        pred_y, pred_dy, y, dy, noise_vec, noise_mask, row_mask, weights, stats = ctx.saved_tensors
+        N, nB, mean, std, nstd = ctx.consts
+        d_loss = d_loss.to(torch.float32)
+        d_pred_y, d_pred_dy = torch.empty_like(pred_y), torch.empty_like(pred_dy)
+        call("eqf_dens_loss_bwd", _p(d_loss), _p(pred_y), _p(y), _p(pred_dy), _p(dy), _p(noise_vec),
+             ctypes.c_void_p(_nonnull(noise_mask)), _p(row_mask), _p(weights), _p(stats), N, nB, mean, std, nstd,
+             _p(d_pred_y), _p(d_pred_dy), _stream())
+        return d_pred_y, d_pred_dy, None, None, None, None, None, None, None, None, None, None
+
+
+def dens_loss(pred_y, pred_dy, y, dy, noise_vec, noise_mask, weights, task_mean, task_std, noise_std, row_mask=None,
+              stats_out=None):
+    """loss (0-dim) = w_e mean|pred_y - (y - mean) / std| + w_f mean||pred_dy - dy / std|| over the rows with noise_mask 0
+    + w_d mean||pred_dy - noise_vec / noise_std|| over those with noise_mask 1 [ref: main_md17_dens.py:389-403]; one launch
+    forward, one backward, nothing read back.  weights: [3] fp32 DEVICE tensor {energy, force, denoising}; row_mask: [N] fp32,
+    1 real / 0 phantom (the node_mask of a padded batch), None = all real.  stats_out: the caller's 8-float device buffer
+    {loss_e, loss_f, loss_d, n_f, n_d, mae_e, mae_f, mae_d} (:417-427) -- the same address in every captured bucket; the
+    backward reads the two counts from it, so a buffer shared between calls is backpropagated before the next forward (None: a
+    fresh one per call).  An empty row set contributes an exact 0."""
+    y = _c(y.detach().to(torch.float32).reshape(-1))
+    dy, noise_vec = _c(dy.detach()), _c(noise_vec.detach())
+    _chk(pred_y, pred_dy, y, dy, noise_vec, row_mask, weights, stats_out)
+    N, nB = pred_dy.shape[0], pred_y.numel()
+    if nB < 1 or y.numel() != nB or tuple(pred_dy.shape) != (N, 3) or tuple(dy.shape) != (N, 3) or tuple(noise_vec.shape) != (N, 3):
+        raise ValueError("dens_loss: pred_y %s, y %s, pred_dy %s, dy %s, noise_vec %s" % (
+            tuple(pred_y.shape), tuple(y.shape), tuple(pred_dy.shape), tuple(dy.shape), tuple(noise_vec.shape)))
+    noise_mask = _mask_u8(noise_mask, N)
+    if row_mask is not None and row_mask.numel() != N:
+        raise ValueError("row_mask has %d entries, the batch has %d rows" % (row_mask.numel(), N))
+    if weights.numel() != 3 or weights.dtype != torch.float32:
+        raise ValueError("weights: 3 fp32 device words {energy, force, denoising}")
+    if stats_out is None:
+        stats_out = torch.empty(8, device=pred_y.device, dtype=torch.float32)
+    elif stats_out.numel() != 8 or stats_out.dtype != torch.float32:
+        raise ValueError("stats_out: an 8-float device buffer")
+    return _DensLoss.apply(pred_y, pred_dy, y, dy, noise_vec, noise_mask, row_mask, weights, stats_out, task_mean, task_std,
+                           noise_std)
+
+
 class _RbfGaussian(Function):
     @staticmethod
     def forward(ctx, length, mean, std, weight, bias, cutoff):

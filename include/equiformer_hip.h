@@ -600,6 +600,52 @@ int eqf_edge_geom_bwd2(const float* vec, const float* d_sh, const float* d_len, 
                        float* g_vec, float* g_dsh, float* g_dlen, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The DeNS training step around the model: corruption of a batch, loss + metrics
+ * ------------------------------------------------------------------------------------------- */
+
+/* Masked Gaussian noise on the positions, one launch.  [ref: main_md17_dens.py:514-548 add_masked_gaussian_noise_to_pos]
+ *   denoising_pos_mask[i] = u_mol(batch[i]) < prob            one uniform draw per MOLECULE, the same for all its atoms
+ *   noise_mask[i]         = denoising_pos_mask[i] && (corrupt_ratio < 0 || u_atom(i) < corrupt_ratio)
+ *   noise_vec[i, c]       = std * n(3 i + c)                   every row, masked or not (as the reference fills them)
+ *   force[i]              = noise_mask[i] ? dy[i] : 0
+ *   pos_out[i]            = noise_mask[i] ? pos[i] + noise_vec[i] : pos[i]       (fp32 sum of the STORED noise; else bitwise)
+ * corrupt_ratio < 0: no per-atom draw (the reference's corrupt_ratio=None).  Every random number is a pure function of
+ * (seed, a stream tag, an index: the molecule id, the row, 3 row + c): the same bits on every run and for every launch
+ * geometry.  Uniforms lie in [0, 1) (24 bits: prob = 1 selects everything, prob = 0 nothing), normals come by Box-Muller
+ * with the radial uniform in (0, 1].  Masks are one byte per row, 0 or 1.  pos_out may alias pos.  `seed` is by value: this
+ * launch moves atoms, so it precedes the radius graph of the step and stays outside a HIP-graph capture. */
+int eqf_dens_corrupt(const float* pos, const float* dy, const int* batch, int N, float std, float prob,
+                     float corrupt_ratio, unsigned long long seed, float* pos_out, float* force, float* noise_vec,
+                     unsigned char* noise_mask, unsigned char* denoising_pos_mask, void* stream);
+
+/* The three-term DeNS loss and the step's metrics, one launch.  [ref: main_md17_dens.py:389-403 the losses (L2MAELoss:
+ * mean over rows of the L2 norm of the row), :417-427 the MAE meters]
+ *   loss_e = mean_b |pred_y[b] - (y[b] - task_mean) / task_std|                             b < nB
+ *   loss_f = mean ||pred_dy[i] - dy[i] / task_std||_2          over real rows with noise_mask 0   (n_f rows)
+ *   loss_d = mean ||pred_dy[i] - noise_vec[i] / noise_std||_2  over real rows with noise_mask 1   (n_d rows)
+ *   loss[0] = weights[0] loss_e + weights[1] loss_f + weights[2] loss_d
+ *   stats[8] = {loss_e, loss_f, loss_d, n_f, n_d, mae_e, mae_f, mae_d},  mae_e = mean |pred_y task_std + task_mean - y|,
+ *   mae_f / mae_d = mean over the rows of the set and their 3 components of |pred_dy task_std - dy| /
+ *   |pred_dy noise_std - noise_vec|.
+ * A term whose row set is empty contributes exactly 0 and its loss / MAE entries are 0 (the reference gets NaN from the
+ * empty mean and skips the term).  row_mask [N] (1 real, 0 phantom: the node_mask of a padded batch) may be NULL = all rows
+ * real; phantom rows are never read.  `weights` [3] is DEVICE memory: a launch captured in a HIP graph sees a weight the
+ * host changed between two replays (the linear decay of the denoising weight).  One workgroup, fp64 arithmetic from the
+ * fp32 inputs, fixed-order reduction: no atomics, no workspace, two calls give the same bits.  nB < 1 is an argument
+ * error, N == 0 is legal. */
+int eqf_dens_loss_fwd(const float* pred_y, const float* y, const float* pred_dy, const float* dy, const float* noise_vec,
+                      const unsigned char* noise_mask, const float* row_mask, const float* weights, int N, int nB,
+                      double task_mean, double task_std, double noise_std, float* loss, float* stats, void* stream);
+/* d_pred_y[nB] = g w_e / nB sign(e), d_pred_dy[N,3] = g w / n d / ||d|| with the weight and the count (stats[3] / stats[4] of
+ * the forward) of the row's own set; exactly 0 where ||d|| = 0 (the subgradient torch takes) and on phantom rows.
+ * g = d_loss[0], read on the device.  First order only: pred_dy carries the second-order graph of the forces, the loss
+ * does not.  [ref: the `loss.backward()` of main_md17_dens.py:406 through :389-403] */
+int eqf_dens_loss_bwd(const float* d_loss, const float* pred_y, const float* y, const float* pred_dy, const float* dy,
+                      const float* noise_vec, const unsigned char* noise_mask, const float* row_mask, const float* weights,
+                      const float* stats, int N, int nB, double task_mean, double task_std, double noise_std,
+                      float* d_pred_y, float* d_pred_dy, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; used by bench.py for the roofline line)
  * ------------------------------------------------------------------------------------------- */
 
