@@ -46,7 +46,17 @@ class EqfDtpPaths(ctypes.Structure):
                 ("out_off", _PA), ("out_ch", _PA), ("out_k", _PA), ("w_off", _PA), ("cg_off", _PA), ("m_off", _PA)]
 
 
+_SA = c_int * EQF_MAX_SEG
+
+
+class EqfEdgeDeg(ctypes.Structure):
+    _fields_ = [("nblk", c_int), ("C", c_int), ("H", c_int), ("w_numel", c_int), ("pw_numel", c_int), ("m_numel", c_int),
+                ("Z", c_int), ("D", c_int), ("l", _SA), ("N", _SA), ("K", _SA), ("w_off", _SA), ("out_ch", _SA),
+                ("pw_off", _SA), ("m_off", _SA), ("node_off", _SA), ("z_off", _SA)]
+
+
 _P_IRR = ctypes.POINTER(EqfIrreps)
+_P_EDEG = ctypes.POINTER(EqfEdgeDeg)
 _P_PATHS = ctypes.POINTER(EqfDtpPaths)
 _PP = ctypes.POINTER(ctypes.c_void_p)
 _f = ctypes.c_float
@@ -131,6 +141,10 @@ SIGNATURES = {
     "eqf_dp_logits_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp],
     "eqf_dp_logits_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp],
     "eqf_vec_sh": [c_fp, c_fp, c_int, c_int, _f, c_fp, c_fp],
+    "eqf_edgedeg_fold_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, _P_EDEG, c_fp, c_fp, c_fp],
+    "eqf_edgedeg_fold_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, _P_EDEG, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "eqf_edgedeg_scatter_fwd": [c_fp, c_fp, c_fp, c_fp, _P_EDEG, _f, c_fp, c_int, c_int, c_fp],
+    "eqf_edgedeg_scatter_bwd": [c_fp, c_fp, c_fp, c_fp, _P_EDEG, _f, c_fp, c_fp, c_int, c_int, c_fp],
     "eqf_segment_scale": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
     "eqf_dtp_fwd": [c_fp, c_fp, c_fp, _P_PATHS, c_fp, c_int, c_fp],
     "eqf_dtp_bwd": [c_fp, c_fp, c_fp, _P_PATHS, c_fp, c_fp, c_fp, c_fp, c_int, c_fp],

@@ -154,7 +154,9 @@ class _Trunk(nn.Module):
         # the radial MLPs of all blocks side by side (RadialBank): first- and second-order (forces taken with create_graph:
         # MD17 / DeNS training) alike since round 5
         bank = self._radial_bank()
-        ectx = EdgeContext(graph, edge_sh, edge_scalars, radial_bank=bank)
+        # (a collapsed edge-degree embedding reads the hidden activation of its radial MLP, not the per-edge weights)
+        hidden = [self.edge_deg_embed.rad] if self.edge_deg_embed.collapses(edge_sh) else []
+        ectx = EdgeContext(graph, edge_sh, edge_scalars, radial_bank=bank, hidden_only=hidden)
         # residual stream kept as a lazy pair (a, b) = a + b: each add is folded into the layer norm that consumes it
         a, b = node_embedding, self.edge_deg_embed(node_embedding, ectx)
         if extra is not None:  # a further per-node term of the input embedding (DeNS force encoding)

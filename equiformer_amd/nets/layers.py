@@ -308,14 +308,15 @@ class RadialProfile(nn.Module):
         bound = 1 / math.sqrt(ch_list[-2])
         nn.init.uniform_(self.offset, -bound, bound)
 
-    def forward(self, f_in):
+    def forward(self, f_in, hidden_only=False):
+        """hidden_only: stop in front of the last layer (its consumer folds that layer into its own weights)"""
         x = f_in
         mods = list(self.net)
         i = 0
         while i < len(mods):
             lin = mods[i]
             if i == len(mods) - 1:
-                return ops.dense_linear(x, lin.weight, self.offset)  # y = x W^T + offset
+                return x if hidden_only else ops.dense_linear(x, lin.weight, self.offset)  # y = x W^T + offset
             ln = mods[i + 1]
             x = ops.dense_linear(x, lin.weight, lin.bias)
             x = ops.ln_silu(x, ln.weight, ln.bias, ln.eps)
@@ -348,8 +349,10 @@ class RadialBank:
     # backward) cost more than the grouped ones save in HBM reads.  The banked form stays the default.
     LAST_BANKED = os.environ.get("EQF_RADIAL_LAST_BANKED", "1") == "1"
 
-    def forward(self, edge_scalars):
-        """-> {id(module): [E, weight_numel]} (LAST_BANKED) or {id(module): hidden activation [E, 64] of the module's last layer}"""
+    def forward(self, edge_scalars, hidden_only=()):
+        """-> {id(module): [E, weight_numel]} (LAST_BANKED) or {id(module): hidden activation [E, 64] of the module's last layer}.
+        The modules in `hidden_only` are left out of the grouped last layer (their consumer wants the hidden activation: the
+        collapsed edge-degree embedding) and get their hidden activation whatever LAST_BANKED says."""
         ms = self.modules
         G = len(ms)
         C = ms[0].net[0].weight.shape[0]
@@ -359,8 +362,17 @@ class RadialBank:
         h = ops.grouped_linear(h, C, [m.net[3].weight for m in ms], [m.net[3].bias for m in ms], wide=True)
         h = ops.ln_silu(h, cat([m.net[4].weight for m in ms]), cat([m.net[4].bias for m in ms]), ms[0].net[4].eps, groups=G)
         if self.LAST_BANKED:
-            outs = ops.grouped_linear(h, C, [m.net[6].weight for m in ms], [m.offset for m in ms], wide=False)
-            return {id(m): o for m, o in zip(ms, outs)}
+            hid = {id(m) for m in hidden_only}
+            cols = [g for g, m in enumerate(ms) if id(m) not in hid]
+            rest = [m for m in ms if id(m) in hid]
+            if not rest:
+                outs = ops.grouped_linear(h, C, [m.net[6].weight for m in ms], [m.offset for m in ms], wide=False)
+                return {id(m): o for m, o in zip(ms, outs)}
+            if not cols:
+                return {id(m): hg for m, hg in zip(ms, ops.split_columns(h, G))}
+            last = [ms[g] for g in cols]
+            outs = ops.grouped_linear(h, C, [m.net[6].weight for m in last], [m.offset for m in last], wide=False, cols=cols)
+            return {id(m): o for m, o in zip(last + rest, outs)}
         return {id(m): hg for m, hg in zip(ms, ops.split_columns(h, G))}
 
     @staticmethod
@@ -429,21 +441,39 @@ class EdgeContext:
     """Per-forward geometry shared by every block: the dst-sorted graph, spherical harmonics, radial basis and
     the DTP coupling matrices (one tensor per distinct path table, computed once per forward)."""
 
-    def __init__(self, graph, edge_sh, edge_scalars, radial_bank=None):
+    def __init__(self, graph, edge_sh, edge_scalars, radial_bank=None, hidden_only=()):
+        """hidden_only: RadialProfile modules whose consumer asks for `radial_hidden` instead of `radial`"""
         self.graph, self.edge_sh, self.edge_scalars = graph, edge_sh, edge_scalars
         self._coupling = {}
         self._bank, self._radial = radial_bank, None
+        self._hidden_only = tuple(hidden_only)
+
+    def _banked(self, module):
+        if self._bank is None:
+            return None
+        if self._radial is None:
+            self._radial = self._bank.forward(self.edge_scalars, self._hidden_only)
+        return self._radial.get(id(module))
+
+    def wants_hidden(self, module):
+        return any(m is module for m in self._hidden_only)
 
     def radial(self, module):
         """Per-edge path weights of `module` (a RadialProfile): from the model's radial bank when there is one (all
         modules evaluated together on first use), otherwise the module on its own."""
-        if self._bank is not None:
-            if self._radial is None:
-                self._radial = self._bank.forward(self.edge_scalars)
-            w = self._radial.get(id(module))
-            if w is not None:
-                return w if self._bank.LAST_BANKED else self._bank.last_layer(module, w)
+        w = self._banked(module)
+        if w is not None:
+            if self._bank.LAST_BANKED and not self.wants_hidden(module):
+                return w
+            return self._bank.last_layer(module, w)
         return module(self.edge_scalars)
+
+    def radial_hidden(self, module):
+        """Hidden activation [E, 64] in front of the last layer of `module`, which must have been named in `hidden_only`: from
+        the bank (which then leaves the module's last layer out of its grouped launch), otherwise the module's own layers."""
+        assert self.wants_hidden(module)
+        h = self._banked(module)
+        return h if h is not None else module(self.edge_scalars, hidden_only=True)
 
     def coupling(self, table):
         c = self._coupling.get(table.key)
@@ -916,9 +946,29 @@ class EdgeDegreeEmbeddingNetwork(nn.Module):
         self.D = self.exp.layout_out.dim
         self.C = self.exp.layout_out.mul_of(0)
         self.use_fused = True
+        self.collapsed_spec = ops.EdgeDegSpec(self.dw.table, self.proj.spec, self.rad.net[-1].weight.shape[1])
+
+    # src_features is exp(ones): the same row for every edge, zeros outside the C channels of 0e.  Only the l1 == 0 paths of the
+    # table see anything else; radial last layer, depth-wise product and projection fold into one [sum N_l, 64] matrix and the
+    # operator becomes one E x 64 GEMM and a segmented scatter (csrc/edgedeg.hip).  EQF_EDGE_DEGREE_COLLAPSED=0 keeps the fused
+    # SeparableFCTP (A/B measurements of one build).
+    use_collapsed = os.environ.get("EQF_EDGE_DEGREE_COLLAPSED", "1") == "1"
+
+    def collapses(self, edge_sh):
+        """The collapsed path applies: fused kernels asked for, an SE(3) table, and nothing differentiates through the
+        spherical harmonics (force training keeps the fused operator, also at second order)."""
+        return bool(self.use_collapsed and self.use_fused is True and self.sfc_spec.supported and self.collapsed_spec.supported
+                    and self.collapsed_spec.C == self.C and not edge_sh.requires_grad)
 
     def forward(self, node_input, ectx):
         g = ectx.graph
+        if self.collapses(ectx.edge_sh) and ectx.wants_hidden(self.rad):
+            spec = self.collapsed_spec
+            At, a = ops.edgedeg_fold(self.rad.net[-1].weight, self.rad.offset, self.exp.tp.weight, self.exp._bias(),
+                                     self.proj.tp.weight, spec)
+            z = ops.dense_linear(ectx.radial_hidden(self.rad), At, a)
+            return ops.edgedeg_scatter(z, ectx.coupling(self.dw.table), self.proj._bias(), g, spec,
+                                       1.0 / (self.scale_scatter.avg_aggregate_num ** 0.5))
         # exp(ones): the same row for every node == lookup of row 0
         zeros = torch.zeros(g.N, dtype=torch.int32, device=node_input.device)
         node_features = ops.embed(zeros, self.exp.tp.weight.view(1, self.C), self.exp._bias(), self.D)

@@ -754,10 +754,11 @@ def _lin_wgrad(x, dy, spec, dw, db=None):
 
 
 # ------------------------------------------------------------------------------------------------- grouped / dense linear
-def _glin_fwd_descs(x, ldx, K, wide, Ws, bs):
-    """y_g = x[:, g K:(g+1) K] W_g^T (+ b_g), W_g [N_g, K]: (one [rows, sum N] tensor if `wide`, else a tuple; descriptors).
-    `ldx` is the row stride of x."""
+def _glin_fwd_descs(x, ldx, K, wide, Ws, bs, cols=None):
+    """y_g = x[:, c_g K:(c_g+1) K] W_g^T (+ b_g), W_g [N_g, K]: (one [rows, sum N] tensor if `wide`, else a tuple; descriptors).
+    `ldx` is the row stride of x; `cols` the column blocks c_g of x the groups read (default: c_g = g)."""
     G = len(Ws)
+    cols = range(G) if cols is None else cols
     rows_n = x.shape[0]
     Ns = [int(W.shape[0]) for W in Ws]
     if wide:
@@ -766,24 +767,27 @@ def _glin_fwd_descs(x, ldx, K, wide, Ws, bs):
     else:
         outs = [torch.empty((rows_n, n), device=x.device, dtype=torch.float32) for n in Ns]
         ldo, offs = None, [0] * G
-    descs = [_desc(1, (x, g * K), rows(1, ldx, 0), (Ws[g], 0), K, (outs[g], offs[g]),
+    descs = [_desc(1, (x, cols[g] * K), rows(1, ldx, 0), (Ws[g], 0), K, (outs[g], offs[g]),
                    rows(1, ldo if wide else Ns[g], 0), bs[g], rows_n, Ns[g], K) for g in range(G)]
     return (out if wide else tuple(outs)), descs
 
 
-def _glin_dgrad_descs(dyt, offs, ldd, Ws, K, rows_n):
-    """dx[:, g K:(g+1) K] = dy_g W_g"""
+def _glin_dgrad_descs(dyt, offs, ldd, Ws, K, rows_n, cols=None, Gx=None):
+    """dx[:, c_g K:(c_g+1) K] = dy_g W_g; dx has Gx column blocks (default G), those outside `cols` are left unwritten"""
     G = len(Ws)
+    cols = range(G) if cols is None else cols
+    Gx = G if Gx is None else Gx
     Ns = [int(W.shape[0]) for W in Ws]
-    dx = torch.empty((rows_n, G * K), device=dyt[0].device, dtype=torch.float32)
-    return dx, [_desc(0, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else Ns[g], 0), (Ws[g], 0), K, (dx, g * K),
-                      rows(1, G * K, 0), None, rows_n, K, Ns[g]) for g in range(G)]
+    dx = torch.empty((rows_n, Gx * K), device=dyt[0].device, dtype=torch.float32)
+    return dx, [_desc(0, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else Ns[g], 0), (Ws[g], 0), K, (dx, cols[g] * K),
+                      rows(1, Gx * K, 0), None, rows_n, K, Ns[g]) for g in range(G)]
 
 
-def _glin_wgrad_descs(dyt, offs, ldd, x, ldx, K, dWs, dbs):
+def _glin_wgrad_descs(dyt, offs, ldd, x, ldx, K, dWs, dbs, cols=None):
     """dW_g[N_g, K] (zero-initialised) += dy_g^T x_g; db_g (zero-initialised, optional) += column sums of dy_g (same launch).
     (kind 3: `rc` carries the row stride of x and ldb the leading dimension of dW_g)"""
-    return [_desc(3, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else dW.shape[0], 0), (x, g * K), K, (dW, 0),
+    cols = range(len(dWs)) if cols is None else cols
+    return [_desc(3, (dyt[g], offs[g]), rows(1, ldd if ldd is not None else dW.shape[0], 0), (x, cols[g] * K), K, (dW, 0),
                   rows(1, ldx, 0), dbs[g], dW.shape[0], K, x.shape[0]) for g, dW in enumerate(dWs)]
 
 
@@ -1192,15 +1196,15 @@ def _glin_views(dys, wide, Ns, rows_n, dev):
     return dyt, [0] * G, None
 
 
-def _glin_fwd(x, K, wide, Ws, bs):
-    return _launch(_glin_fwd_descs(x, x.shape[1], K, wide, Ws, bs))
+def _glin_fwd(x, K, wide, Ws, bs, cols=None):
+    return _launch(_glin_fwd_descs(x, x.shape[1], K, wide, Ws, bs, cols))
 
 
-def _glin_dgrad(dyt, offs, ldd, Ws, K, rows_n):
-    return _launch(_glin_dgrad_descs(dyt, offs, ldd, Ws, K, rows_n))
+def _glin_dgrad(dyt, offs, ldd, Ws, K, rows_n, cols=None, Gx=None):
+    return _launch(_glin_dgrad_descs(dyt, offs, ldd, Ws, K, rows_n, cols, Gx))
 
 
-def _glin_wgrad(dyt, offs, ldd, x, K, Ns, has_b):
+def _glin_wgrad(dyt, offs, ldd, x, K, Ns, has_b, cols=None):
     """(dW_g, db_g or None) of all groups in one launch; one zero-filled flat buffer behind all of them (a captured step counts
     fill nodes)"""
     flat = _zeros(sum(n * K for n in Ns) + sum(n for n, hb in zip(Ns, has_b) if hb), x.device)
@@ -1211,7 +1215,7 @@ def _glin_wgrad(dyt, offs, ldd, x, K, Ns, has_b):
     for n, hb in zip(Ns, has_b):
         dbs.append(flat[o:o + n] if hb else None)
         o += n if hb else 0
-    _gemm_group(_glin_wgrad_descs(dyt, offs, ldd, x, x.shape[1], K, dWs, dbs), _stream())
+    _gemm_group(_glin_wgrad_descs(dyt, offs, ldd, x, x.shape[1], K, dWs, dbs, cols), _stream())
     return dWs, dbs
 
 
@@ -1285,46 +1289,66 @@ class _GroupedLinear(Function):
     when forces are taken, MD17 / DeNS training)."""
 
     @staticmethod
-    def forward(ctx, x, K, wide, *params):
+    def forward(ctx, x, K, wide, cols, *params):
         G = len(params) // 2
         Ws, bs = params[:G], params[G:]
         x = _c(x)
         _chk(x, *Ws, *bs)
         rows_n, ldx = x.shape
         Ns = [int(W.shape[0]) for W in Ws]
-        assert ldx == G * K and all(W.shape[1] == K and W.is_contiguous() for W in Ws)
-        out = _glin_fwd(x, K, wide, list(Ws), list(bs))
+        Gx = ldx // K
+        cols = tuple(range(G)) if cols is None else tuple(cols)
+        rest = tuple(g for g in range(Gx) if g not in cols)  # column blocks handed through (their consumer reads them itself)
+        assert ldx == Gx * K and len(cols) == G and all(W.shape[1] == K and W.is_contiguous() for W in Ws)
+        assert not (rest and wide) and len(set(cols)) == G and all(0 <= c < Gx for c in cols)
+        out = _glin_fwd(x, K, wide, list(Ws), list(bs), cols)
         ctx.save_for_backward(x, *Ws)
-        ctx.meta = (G, K, wide, Ns, [b is not None for b in bs])
+        ctx.meta = (G, K, wide, Ns, [b is not None for b in bs], cols, rest)
+        if rest:
+            out = out + tuple(x[:, g * K:(g + 1) * K].contiguous() for g in rest)
         return out
 
     @staticmethod
     def backward(ctx, *dys):
         x, *Ws = ctx.saved_tensors
-        G, K, wide, Ns, has_b = ctx.meta
+        G, K, wide, Ns, has_b, cols, rest = ctx.meta
         rows_n, ldx = x.shape
         dev = x.device
+        dys, drest = dys[:len(dys) - len(rest)], dys[len(dys) - len(rest):]
         if torch.is_grad_enabled():  # create_graph: every piece is itself differentiable
             dlist = [dys[0]] if wide else [(d if d is not None else _zeros((rows_n, Ns[g]), dev)) for g, d in enumerate(dys)]
+            xs = x if not rest else torch.cat([x[:, c * K:(c + 1) * K] for c in cols], 1)
             dx = _GroupedDgrad.apply(K, wide, G, *dlist, *Ws) if ctx.needs_input_grad[0] else None
+            if dx is not None and rest:
+                blocks = {c: dx[:, g * K:(g + 1) * K] for g, c in enumerate(cols)}
+                for g, d in zip(rest, drest):
+                    blocks[g] = d if d is not None else _zeros((rows_n, K), dev)
+                dx = torch.cat([blocks[g] for g in range(ldx // K)], 1)
             if not _want_param_grads():
-                return (dx, None, None) + (None,) * (2 * G)
-            outs = _GroupedWgrad.apply(K, wide, tuple(Ns), tuple(has_b), x, *dlist)
+                return (dx, None, None, None) + (None,) * (2 * G)
+            outs = _GroupedWgrad.apply(K, wide, tuple(Ns), tuple(has_b), xs, *dlist)
             it = iter(outs[G:])
-            return (dx, None, None) + tuple(outs[:G]) + tuple((next(it) if hb else None) for hb in has_b)
+            return (dx, None, None, None) + tuple(outs[:G]) + tuple((next(it) if hb else None) for hb in has_b)
         dyt, offs, ldd = _glin_views(dys, wide, Ns, rows_n, dev)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = _glin_dgrad(dyt, offs, ldd, list(Ws), K, rows_n)
+            dx = _glin_dgrad(dyt, offs, ldd, list(Ws), K, rows_n, cols, ldx // K)
+            for g, d in zip(rest, drest):
+                if d is None:
+                    dx[:, g * K:(g + 1) * K].zero_()
+                else:
+                    dx[:, g * K:(g + 1) * K].copy_(d)
         if not _want_param_grads():
-            return (dx, None, None) + (None,) * (2 * G)
+            return (dx, None, None, None) + (None,) * (2 * G)
         # kind 3: dW_g[N_g, K] += dy_g^T x_g, db_g += column sums of dy_g (same launch)
-        dWs, dbs = _glin_wgrad(dyt, offs, ldd, x, K, Ns, has_b)
-        return (dx, None, None) + tuple(dWs) + tuple(dbs)
+        dWs, dbs = _glin_wgrad(dyt, offs, ldd, x, K, Ns, has_b, cols)
+        return (dx, None, None, None) + tuple(dWs) + tuple(dbs)
 
 
-def grouped_linear(x, K, weights, biases, wide):
-    return _GroupedLinear.apply(x, int(K), bool(wide), *weights, *biases)
+def grouped_linear(x, K, weights, biases, wide, cols=None):
+    """`cols`: the column blocks of x the G layers read, when x has more blocks than there are layers (wide=False only): the
+    blocks left over are returned behind the G outputs, as copies, and their gradients go into dx beside the layers' own."""
+    return _GroupedLinear.apply(x, int(K), bool(wide), None if cols is None else tuple(cols), *weights, *biases)
 
 
 class _FoldWeight(Function):
@@ -1391,6 +1415,132 @@ class _Embed(Function):
 def embed(types, W, b, D):
     """W: [num_types, C] (row lookup), b: [C]; output rows [D] with columns >= C zero."""
     return _Embed.apply(types, _c(W), b, D)
+
+
+# ------------------------------------------------------------------------------------------------- collapsed edge-degree embedding
+class EdgeDegSpec:
+    """The l1 == 0 paths of an EdgeDegreeEmbeddingNetwork's path table paired with the [K, N] blocks of its projection: all
+    that is left of the SeparableFCTP when its input is exp(ones), the same row for every edge with zeros outside the C
+    channels of the 0e segment (csrc/edgedeg.hip).  The paths are FOUND in the table (input segment 0e, even output), not
+    assumed to come first.  `table`: DtpTable, `proj`: LinearSpec of the projection, `hidden`: width of the radial hidden
+    activation."""
+
+    def __init__(self, table, proj, hidden):
+        self.table, self.proj = table, proj
+        lay = table.layout_in
+        i0 = lay.seg_index(0, 1)
+        blocks = []
+        if i0 is not None:
+            for p in table.paths:
+                if p["l1"] != 0 or p["p3"] != 1 or p["in_off"] != lay.offsets[i0]:
+                    continue
+                for (l, in_off, K, out_off, N, w_off) in proj.pairs:
+                    if in_off == p["out_off"]:
+                        blocks.append(dict(l=l, N=N, K=K, w_off=p["w_off"], out_ch=p["out_ch"], pw_off=w_off, m_off=p["m_off"],
+                                           node_off=out_off))
+        blocks.sort(key=lambda b: b["l"])
+        self.blocks = blocks
+        self.C = lay.segs[i0][0] if i0 is not None else 0
+        self.Z = sum(b["N"] for b in blocks)
+        self.D = proj.out_layout.dim
+        # every column of the node rows is written by a block (otherwise the scatter starts from zeros)
+        self.covers = sum((2 * b["l"] + 1) * b["N"] for b in blocks) == self.D
+        self.has_bias_block = any(b["l"] == 0 for b in blocks)
+        self.supported = (not table.has_odd and not proj.out_layout.has_odd and 0 < len(blocks) <= lib.EQF_MAX_SEG
+                          and all(b["l"] <= 3 for b in blocks))
+        c = lib.EqfEdgeDeg()
+        c.nblk, c.C, c.H, c.w_numel, c.pw_numel = len(blocks), self.C, int(hidden), table.weight_numel, proj.weight_numel
+        c.m_numel, c.Z, c.D = table.m_numel, self.Z, self.D
+        z = 0
+        for i, b in enumerate(blocks[:lib.EQF_MAX_SEG]):
+            for k in ("l", "N", "K", "w_off", "out_ch", "pw_off", "m_off", "node_off"):
+                getattr(c, k)[i] = b[k]
+            c.z_off[i] = z
+            z += b["N"]
+        self.c = c
+
+    @property
+    def c_ref(self):
+        return ctypes.byref(self.c)
+
+
+class _EdgeDegFold(Function):
+    """(W3, offset, exp weight, exp bias, projection weight) -> At [Z, H], a [Z] with z = h At^T + a (eqf_edgedeg_fold_*).
+    The backward WRITES every entry of the five parameter gradients: the rows no l1 == 0 path reads are exact zeros."""
+
+    @staticmethod
+    def forward(ctx, W3, offset, expw, expb, W, spec):
+        W3, offset, expw, W = _c(W3), _c(offset), _c(expw), _c(W)
+        _chk(W3, offset, expw, expb, W)
+        c = spec.c
+        assert tuple(W3.shape) == (c.w_numel, c.H) and offset.numel() == c.w_numel and expw.numel() == c.C
+        assert W.numel() == c.pw_numel and (expb is None or expb.numel() == c.C)
+        At = torch.empty((c.Z, c.H), device=W3.device, dtype=torch.float32)
+        a = torch.empty(c.Z, device=W3.device, dtype=torch.float32)
+        call("eqf_edgedeg_fold_fwd", _p(W3), _p(offset), _p(expw), _p(expb), _p(W), spec.c_ref, _p(At), _p(a), _stream())
+        ctx.save_for_backward(W3, offset, expw, expb, W)
+        ctx.spec = spec
+        return At, a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dAt, da):
+        W3, offset, expw, expb, W = ctx.saved_tensors
+        spec = ctx.spec
+        dev = W3.device
+        dAt = _c(dAt) if dAt is not None else _zeros((spec.c.Z, spec.c.H), dev)
+        da = _c(da) if da is not None else _zeros(spec.c.Z, dev)
+        _chk(dAt, da)
+        dW3, doffset, dW = torch.empty_like(W3), torch.empty_like(offset), torch.empty_like(W)
+        dx0 = torch.empty_like(expw)
+        call("eqf_edgedeg_fold_bwd", _p(W3), _p(offset), _p(expw), _p(expb), _p(W), spec.c_ref, _p(dAt), _p(da), _p(dW3),
+             _p(doffset), _p(dW), _p(dx0), _stream())
+        # x0 = exp weight + exp bias: one gradient, two owners (two tensors: AccumulateGrad adopts what it is handed)
+        return dW3, doffset, dx0, (dx0.clone().view(expb.shape) if expb is not None else None), dW, None
+
+
+def edgedeg_fold(W3, offset, expw, expb, W, spec):
+    return _EdgeDegFold.apply(W3, offset, expw, expb, W, spec)
+
+
+class _EdgeDegScatter(Function):
+    """node[i] = scale * (sum over the incoming edges of coupling (x) z + deg(i) bias on 0e) (eqf_edgedeg_scatter_*): segmented
+    over the dst-sorted CSR, no atomics.  First order, coupling constant: a coupling that needs a gradient (forces) is refused."""
+
+    @staticmethod
+    def forward(ctx, z, coupling, bias, graph, spec, scale):
+        if ctx.needs_input_grad[1]:
+            raise HipOnlyError("the collapsed edge-degree embedding has no gradient wrt the coupling (use_collapsed=False)")
+        z, coupling = _c(z), _c(coupling)
+        _chk(z, coupling, bias, graph.row_ptr, graph.dst)
+        c = spec.c
+        assert z.shape == (graph.E, c.Z) and coupling.shape == (graph.E, c.m_numel)
+        assert bias is None or (spec.has_bias_block and bias.numel() == spec.blocks[0]["N"])
+        node = (torch.empty if spec.covers else torch.zeros)((graph.N, c.D), device=z.device, dtype=torch.float32)
+        call("eqf_edgedeg_scatter_fwd", _p(z), _p(coupling), _p(graph.row_ptr), _p(bias), spec.c_ref, scale, _p(node), graph.N,
+             graph.E, _stream())
+        ctx.save_for_backward(coupling)
+        ctx.args = (graph, spec, scale, bias is not None)
+        return node
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dnode):
+        (coupling,) = ctx.saved_tensors
+        graph, spec, scale, has_b = ctx.args
+        dnode = _c(dnode)
+        _chk(dnode)
+        dz = torch.empty((graph.E, spec.c.Z), device=dnode.device, dtype=torch.float32)
+        db = None
+        if has_b and ctx.needs_input_grad[2] and _want_param_grads():
+            db = torch.empty(spec.blocks[0]["N"], device=dnode.device, dtype=torch.float32)
+        call("eqf_edgedeg_scatter_bwd", _p(dnode), _p(coupling), _p(graph.dst), _p(graph.row_ptr), spec.c_ref, scale, _p(dz),
+             _p(db), graph.N, graph.E, _stream())
+        return dz, None, db, None, None, None
+
+
+def edgedeg_scatter(z, coupling, bias, graph, spec, scale):
+    return _EdgeDegScatter.apply(z, coupling, bias, graph, spec, float(scale))
 
 
 # ------------------------------------------------------------------------------------------------- graph ops

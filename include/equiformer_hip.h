@@ -478,6 +478,45 @@ int eqf_segment_sum(const float* x, const int* ptr, const int* perm, float* out,
 int eqf_segment_bcast(const float* x, const int* seg_of, float* out, int rows, int D, float scale,
                       void* stream);
 
+/* Collapsed edge-degree embedding.  The embedding feeds its SeparableFCTP with the SAME row for every edge: x0[u] =
+ * exp_w[u] + exp_b[u] in the C channels of the 0e segment, zeros elsewhere.  Only the depth-wise paths with l1 == 0 see
+ * anything but zeros -- one per output degree l, its coupling block being the 2l+1 entries coupling[e, m_off .. ] -- and
+ * the radial last layer (W3 [w_numel, H], offset [w_numel]), the depth-wise product and the projection (flat weight W,
+ * [K, N] blocks at pw_off) fold into one small matrix.  Block b of the descriptor is one such path:
+ *   fold_fwd:    At[z_off_b + n, j] = sum_u W_b[out_ch_b + u, n] x0[u] W3[w_off_b + u, j]       (At [Z, H], a [Z] alike
+ *                with offset in the place of W3); the caller computes z[E, Z] = h At^T + a with the dense GEMM.
+ *   fold_bwd:    (dAt, da) -> dW3, doffset, dW (every entry WRITTEN: the rows no l1 == 0 path reads are zeros) and
+ *                dx0[C] (the gradient of exp_w and of exp_b).
+ *   scatter_fwd: node[i, node_off_b + k N_b + n] = scale * (sum_{e in [row_ptr[i], row_ptr[i+1])} coupling[e, m_off_b + k]
+ *                * z[e, z_off_b + n] + [l_b == 0] deg(i) bias[n]); columns of node outside every block are not written.
+ *   scatter_bwd: dz[e, z_off_b + n] = scale * sum_k coupling[e, m_off_b + k] dnode[dst[e], node_off_b + k N_b + n];
+ *                dbias[n] = scale * sum_i deg(i) dnode[i, node_off(l == 0) + n]  (dbias may be NULL).
+ * No atomics, fixed summation orders (bit-reproducible); degrees l <= 3.  exp_b / bias may be NULL.
+ * [ref: EdgeDegreeEmbeddingNetwork nets/graph_attention_transformer.py:709-733 -- exp(ones) :726-727, rad :728,
+ *  dw :729, proj :730, scale_scatter :731-732; RadialProfile's last layer + offset nets/radial_func.py:9-49] */
+typedef struct eqf_edgedeg {
+  int nblk;     /* l1 == 0 paths that reach an output segment (<= EQF_MAX_SEG) */
+  int C;        /* channels of the 0e input segment */
+  int H;        /* width of the radial hidden activation */
+  int w_numel;  /* rows of W3 / entries of offset */
+  int pw_numel; /* entries of the flat projection weight */
+  int m_numel;  /* row length of coupling */
+  int Z;        /* sum_b N[b]: row length of z */
+  int D;        /* row length of node */
+  int l[EQF_MAX_SEG], N[EQF_MAX_SEG], K[EQF_MAX_SEG]; /* degree; columns and rows of the projection block W_b */
+  int w_off[EQF_MAX_SEG], out_ch[EQF_MAX_SEG], pw_off[EQF_MAX_SEG], m_off[EQF_MAX_SEG], node_off[EQF_MAX_SEG];
+  int z_off[EQF_MAX_SEG]; /* ascending: z_off[b+1] = z_off[b] + N[b] */
+} eqf_edgedeg;
+int eqf_edgedeg_fold_fwd(const float* W3, const float* offset, const float* exp_w, const float* exp_b, const float* W,
+                         const eqf_edgedeg* desc, float* At, float* a, void* stream);
+int eqf_edgedeg_fold_bwd(const float* W3, const float* offset, const float* exp_w, const float* exp_b, const float* W,
+                         const eqf_edgedeg* desc, const float* dAt, const float* da, float* dW3, float* doffset, float* dW,
+                         float* dx0, void* stream);
+int eqf_edgedeg_scatter_fwd(const float* z, const float* coupling, const int* row_ptr, const float* bias,
+                            const eqf_edgedeg* desc, float scale, float* node, int nnodes, int E, void* stream);
+int eqf_edgedeg_scatter_bwd(const float* dnode, const float* coupling, const int* dst, const int* row_ptr,
+                            const eqf_edgedeg* desc, float scale, float* dz, float* dbias, int nnodes, int E, void* stream);
+
 /* out[q,:] = s[seg_of[q]] * x[q,:]  (D % 4 == 0; out may alias x).  Per-graph stochastic depth: s holds 0 or
  * 1/keep_prob per graph.  Linear in x: its backward is the same call on dy.
  * [ref: nets/drop.py:45-61 GraphDropPath; nets/graph_attention_transformer.py:652-664] */
