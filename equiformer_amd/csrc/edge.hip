@@ -25,10 +25,10 @@ __global__ __launch_bounds__(256) void gather_add_kernel(const float* __restrict
   reinterpret_cast<float4*>(msg)[idx] = v;
 }
 
-__global__ __launch_bounds__(128) void segment_sum_kernel(const float* __restrict__ x, const int* __restrict__ ptr,
-                                                          const int* __restrict__ perm, float* __restrict__ out, int D,
-                                                          float scale, int accumulate) {
-  const int n = blockIdx.x;
+// segment n of one segmented sum; one workgroup of 128
+__device__ __forceinline__ void segment_sum_block(const float* __restrict__ x, const int* __restrict__ ptr,
+                                                  const int* __restrict__ perm, float* __restrict__ out, int D,
+                                                  float scale, int accumulate, int n) {
   const int beg = ptr[n], end = ptr[n + 1];
   if ((D & 3) == 0) {
     const int D4 = D >> 2;
@@ -70,6 +70,24 @@ __global__ __launch_bounds__(128) void segment_sum_kernel(const float* __restric
       *o = accumulate ? *o + acc : acc;
     }
   }
+}
+
+__global__ __launch_bounds__(128) void segment_sum_kernel(const float* __restrict__ x, const int* __restrict__ ptr,
+                                                          const int* __restrict__ perm, float* __restrict__ out, int D,
+                                                          float scale, int accumulate) {
+  segment_sum_block(x, ptr, perm, out, D, scale, accumulate, (int)blockIdx.x);
+}
+
+// Both adjoints of gather_add read the same d_msg: workgroups [0, nseg) sum by one CSR, [nseg, 2 nseg) by the other -- one
+// launch on the dependency chain instead of two, every segment summed as segment_sum_kernel sums it.
+__global__ __launch_bounds__(128) void segment_sum_pair_kernel(const float* __restrict__ x, const int* __restrict__ ptr_a,
+                                                               const int* __restrict__ perm_a, float* __restrict__ out_a,
+                                                               const int* __restrict__ ptr_b,
+                                                               const int* __restrict__ perm_b, float* __restrict__ out_b,
+                                                               int nseg, int D) {
+  const int b = (int)blockIdx.x;
+  if (b < nseg) segment_sum_block(x, ptr_a, perm_a, out_a, D, 1.f, 0, b);
+  else segment_sum_block(x, ptr_b, perm_b, out_b, D, 1.f, 0, b - nseg);
 }
 
 __global__ __launch_bounds__(256) void segment_bcast_kernel(const float* __restrict__ x, const int* __restrict__ seg_of,
@@ -594,6 +612,16 @@ int eqf_segment_sum(const float* x, const int* ptr, const int* perm, float* out,
   if (nseg <= 0 || D <= 0) return 0;
   hipLaunchKernelGGL(segment_sum_kernel, dim3(nseg), dim3(128), 0, (hipStream_t)stream, x, ptr, perm, out, D, scale,
                      accumulate);
+  EQF_CHECK_LAUNCH();
+  return 0;
+}
+
+int eqf_segment_sum_pair(const float* x, const int* ptr_a, const int* perm_a, float* out_a, const int* ptr_b,
+                         const int* perm_b, float* out_b, int nseg, int D, void* stream) {
+  if (!x || !ptr_a || !out_a || !ptr_b || !out_b || out_a == out_b) return EQF_E_BADARG;
+  if (nseg <= 0 || D <= 0) return 0;
+  hipLaunchKernelGGL(segment_sum_pair_kernel, dim3(2 * nseg), dim3(128), 0, (hipStream_t)stream, x, ptr_a, perm_a, out_a,
+                     ptr_b, perm_b, out_b, nseg, D);
   EQF_CHECK_LAUNCH();
   return 0;
 }

@@ -2,6 +2,8 @@
 // activations, the radial MLP's LayerNorm+SiLU, atom-type embedding and column sums (bias gradients).
 // One wavefront (64 lanes) owns one row; rows are 0.25-3.5 KB, so a row is read once into L1/registers
 // and written once -- algorithmic traffic = 2 x rows x D x 4 bytes.
+#include <limits.h>
+#include <string.h>
 #include "common.h"
 
 namespace {
@@ -146,12 +148,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 // d_weight[woff+u] += sum_rows sum_m dy*xhat ; d_bias[boff+u] += sum_rows dy.   One thread per row column,
 // each block reduces CH rows, atomics at the end (columns of the same channel collide only (2l+1) ways).
 constexpr int LN_WGRAD_ROWS = 64, LN_WGRAD_CHUNK = 16;
-__global__ __launch_bounds__(256) void layernorm_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                              const float* __restrict__ rstd,
-                                                              const float* __restrict__ mean0, float* __restrict__ dw,
-                                                              float* __restrict__ db, int rows, SegTab T) {
+// workgroup (bx, by) of one problem: columns bx * 256 .., rows by * LN_WGRAD_ROWS ..
+__device__ __forceinline__ void layernorm_wgrad_block(const float* __restrict__ x, const float* __restrict__ dy,
+                                                      const float* __restrict__ rstd, const float* __restrict__ mean0,
+                                                      float* __restrict__ dw, float* __restrict__ db, int rows,
+                                                      const SegTab& T, int bx, int by) {
   constexpr int CH = LN_WGRAD_CHUNK;
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  const int c = bx * 256 + threadIdx.x;
   if (c >= T.D) return;
   int s = 0;
   while (s + 1 < T.nseg && c >= T.off[s + 1]) ++s;
@@ -162,7 +165,7 @@ __global__ __launch_bounds__(256) void layernorm_wgrad_kernel(const float* __res
   // (compile-time trip count, rows past the end clamped and masked).  The cost of this kernel is its atomics (same-address
   // fp32 atomics retire at ~0.35 ns each): 64 rows per thread = 37 k of them at 2 304 rows instead of 147 k with 16.
   float aw = 0.f, ab = 0.f;
-  for (int r0 = blockIdx.y * LN_WGRAD_ROWS; r0 < min(rows, (int)(blockIdx.y + 1) * LN_WGRAD_ROWS); r0 += CH) {
+  for (int r0 = by * LN_WGRAD_ROWS; r0 < min(rows, (by + 1) * LN_WGRAD_ROWS); r0 += CH) {
     float gv[CH], xs[CH], rs[CH], m0[CH];
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
@@ -181,6 +184,43 @@ __global__ __launch_bounds__(256) void layernorm_wgrad_kernel(const float* __res
   }
   atomicAdd(dw + T.woff[s] + u, aw);
   if (T.boff[s] >= 0) atomicAdd(db + T.boff[s] + u, ab);
+}
+
+__global__ __launch_bounds__(256) void layernorm_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                              const float* __restrict__ rstd,
+                                                              const float* __restrict__ mean0, float* __restrict__ dw,
+                                                              float* __restrict__ db, int rows, SegTab T) {
+  layernorm_wgrad_block(x, dy, rstd, mean0, dw, db, rows, T, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// The same reduction for up to LNG_MAXP norms in ONE launch: the affine gradients of a norm are parameter gradients only, nothing
+// in backward waits for them, and alone each launch is 72 workgroups on 256 CUs at the latency of its 64-row chain.  One flat
+// grid; workgroup b belongs to problem i with woff[i] <= b < woff[i + 1] (entries past n are INT_MAX), as in gemmx.hip.  A row
+// layout is 236 bytes and the norms of a model share one or two, so the distinct tables are stored once and the problems index them.
+constexpr int LNG_MAXP = 32, LNG_MAXT = 4;
+struct LNGP {
+  const float *x, *dy, *rstd, *mean0;
+  float *dw, *db;
+  int rows, tab;
+};
+struct LNGroup {
+  int n;
+  int woff[LNG_MAXP + 1];
+  SegTab tab[LNG_MAXT];
+  LNGP p[LNG_MAXP];
+};
+static_assert(sizeof(LNGroup) <= 4000, "kernarg segment");
+
+__global__ __launch_bounds__(256) void layernorm_wgrad_group_kernel(LNGroup g) {
+  const int b = (int)blockIdx.x;
+  int pi = 0;
+#pragma unroll
+  for (int j = 1; j < LNG_MAXP; ++j) pi += (int)((unsigned)(g.woff[j] - 1 - b) >> 31);  // sign bit: b >= woff[j]
+  const LNGP& P = g.p[pi];
+  const SegTab& T = g.tab[P.tab];
+  const int local = b - g.woff[pi], nx = (T.D + 255) / 256;
+  const int by = local / nx;
+  layernorm_wgrad_block(P.x, P.dy, P.rstd, P.mean0, P.dw, P.db, P.rows, T, local - by * nx, by);
 }
 
 // ---------------------------------------------------------------------------------------------- gate
@@ -693,6 +733,42 @@ int eqf_add_layernorm_bwd(const float* x, const float* weight, const float* dy, 
   if (d_weight && d_bias) {
     hipLaunchKernelGGL(layernorm_wgrad_kernel, dim3(eqf_cdiv(T.D, 256), eqf_cdiv(rows, LN_WGRAD_ROWS)), dim3(256), 0,
                        (hipStream_t)stream, x, dy, rstd, mean0, d_weight, d_bias, rows, T);
+    EQF_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+int eqf_layernorm_wgrad_group(const eqf_ln_wgrad_desc* d, int n, void* stream) {
+  if (n < 0 || (n > 0 && !d)) return EQF_E_BADARG;
+  for (int i = 0; i < n; ++i) {
+    if (d[i].rows <= 0) continue;
+    if (!d[i].x || !d[i].dy || !d[i].rstd || !d[i].mean0 || !d[i].d_weight || !d[i].d_bias || !d[i].irreps ||
+        d[i].irreps->nseg < 1 || d[i].irreps->nseg > EQF_MAX_SEG)
+      return EQF_E_BADARG;
+  }
+  static thread_local LNGroup G;
+  int i = 0;
+  while (i < n) {  // one launch per LNG_MAXP problems / LNG_MAXT distinct row layouts
+    memset(&G, 0, sizeof G);
+    int ntab = 0, wg = 0;
+    for (; i < n && G.n < LNG_MAXP; ++i) {
+      if (d[i].rows <= 0) continue;
+      const SegTab T = make_segtab(*d[i].irreps);
+      int t = 0;
+      while (t < ntab && memcmp(&G.tab[t], &T, sizeof T) != 0) ++t;
+      if (t == ntab) {
+        if (ntab == LNG_MAXT) break;  // a fifth layout starts the next launch
+        G.tab[ntab++] = T;
+      }
+      LNGP& P = G.p[G.n];
+      P.x = d[i].x, P.dy = d[i].dy, P.rstd = d[i].rstd, P.mean0 = d[i].mean0;
+      P.dw = d[i].d_weight, P.db = d[i].d_bias, P.rows = d[i].rows, P.tab = t;
+      G.woff[G.n++] = wg;
+      wg += eqf_cdiv(T.D, 256) * eqf_cdiv(d[i].rows, LN_WGRAD_ROWS);
+    }
+    if (!G.n) continue;
+    for (int j = G.n; j <= LNG_MAXP; ++j) G.woff[j] = j == G.n ? wg : INT_MAX;
+    hipLaunchKernelGGL(layernorm_wgrad_group_kernel, dim3(wg), dim3(256), 0, (hipStream_t)stream, G);
     EQF_CHECK_LAUNCH();
   }
   return 0;

@@ -33,6 +33,11 @@ class EqfGemmDesc(ctypes.Structure):
                 ("ldb", c_int), ("M", c_int), ("N", c_int), ("K", c_int), ("accumulate", c_int), ("kind", c_int)]
 
 
+class EqfLnWgradDesc(ctypes.Structure):
+    _fields_ = [("x", c_fp), ("dy", c_fp), ("rstd", c_fp), ("mean0", c_fp), ("d_weight", c_fp), ("d_bias", c_fp),
+                ("rows", c_int), ("irreps", ctypes.POINTER(EqfIrreps))]
+
+
 class EqfGateIn(ctypes.Structure):
     _fields_ = [("S", c_int), ("G", c_int), ("c_silu", ctypes.c_float), ("c_sig", ctypes.c_float)]
 
@@ -116,6 +121,7 @@ SIGNATURES = {
     "eqf_sfcx_bwd_weight": [c_fp, c_fp, c_fp, _P_PATHS, c_fp, _P_IRR, c_fp, c_int, _PP, c_fp, c_int, c_int, c_fp],
     "eqf_layernorm_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, _P_IRR, _f, c_fp],
     "eqf_layernorm_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, _P_IRR, c_fp],
+    "eqf_layernorm_wgrad_group": [ctypes.POINTER(EqfLnWgradDesc), c_int, c_fp],
     "eqf_add_layernorm_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, _P_IRR, _f, c_fp],
     "eqf_add_layernorm_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, _P_IRR, c_fp],
     "eqf_graphnorm_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, _P_IRR, _f, c_fp],
@@ -135,6 +141,7 @@ SIGNATURES = {
     "eqf_embed_bwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
     "eqf_gather_add_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
     "eqf_segment_sum": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, _f, c_int, c_fp],
+    "eqf_segment_sum_pair": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
     "eqf_segment_bcast": [c_fp, c_fp, c_fp, c_int, c_int, _f, c_fp],
     "eqf_kv_split": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp],
     "eqf_kv_merge": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp],

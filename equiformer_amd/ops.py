@@ -15,7 +15,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import lib
-from .lib import EqfGemmDesc, EqfRows, call
+from .lib import EqfGemmDesc, EqfLnWgradDesc, EqfRows, call
 
 
 class HipOnlyError(RuntimeError):
@@ -264,8 +264,11 @@ class _LayerNorm(Function):
         _chk(dy)
         dx = torch.empty_like(x)
         dw, db = _zeros2(weight.numel(), ctx.nb, x.device)
-        call("eqf_layernorm_bwd", _p(x), _p(weight), _p(dy), _p(rstd), _p(mean0), _p(dx), _p(dw), _p(db), x.shape[0],
-             ctx.layout.c_ref, _stream())
+        defer = _can_defer(weight, bias)  # the affine gradients wait for the end of the pass (_defer_norm_wgrad)
+        call("eqf_layernorm_bwd", _p(x), _p(weight), _p(dy), _p(rstd), _p(mean0), _p(dx), None if defer else _p(dw),
+             None if defer else _p(db), x.shape[0], ctx.layout.c_ref, _stream())
+        if defer:
+            _defer_norm_wgrad(weight, bias, x, dy, rstd, mean0, ctx.layout, dw, db)
         return dx, dw, db, None, None
 
 
@@ -322,13 +325,13 @@ class _AddLayerNorm(Function):
         mean0 = torch.empty((n, _ln_means(layout)), device=a.device, dtype=torch.float32)
         call("eqf_add_layernorm_fwd", _p(a), _p(b), _p(s), _p(weight), _p(bias), _p(y), _p(rstd), _p(mean0), n,
              layout.c_ref, float(eps), _stream())
-        ctx.save_for_backward(s, weight, rstd, mean0)
+        ctx.save_for_backward(s, weight, rstd, mean0, bias)
         ctx.layout, ctx.nb, ctx.eps = layout, bias.numel(), eps
         return s, y
 
     @staticmethod
     def backward(ctx, ds, dy):
-        s, weight, rstd, mean0 = ctx.saved_tensors
+        s, weight, rstd, mean0, bias = ctx.saved_tensors
         if dy is None:  # the normalised branch is unused: identity on the sum
             return ds, ds, None, None, None, None
         if torch.is_grad_enabled():  # create_graph: differentiable norm backward + a differentiable add
@@ -342,8 +345,11 @@ class _AddLayerNorm(Function):
         d = torch.empty_like(s)
         want = _want_param_grads()
         dw, db = _zeros2(weight.numel(), ctx.nb, s.device) if want else (None, None)
-        call("eqf_add_layernorm_bwd", _p(s), _p(weight), _p(dy), _p(ds), _p(rstd), _p(mean0), _p(d), _p(dw), _p(db), s.shape[0],
-             ctx.layout.c_ref, _stream())
+        defer = want and _can_defer(weight, bias)
+        call("eqf_add_layernorm_bwd", _p(s), _p(weight), _p(dy), _p(ds), _p(rstd), _p(mean0), _p(d),
+             None if defer else _p(dw), None if defer else _p(db), s.shape[0], ctx.layout.c_ref, _stream())
+        if defer:
+            _defer_norm_wgrad(weight, bias, s, dy, rstd, mean0, ctx.layout, dw, db)
         return d, d, dw, db, None, None
 
 
@@ -605,15 +611,16 @@ def _lin_wgrad_descs(x, dy, spec, dw, db=None):
 #     enqueues next), the rest of the pass queues anew.
 
 _defer_wgrad = [os.environ.get("EQF_DEFER_WGRAD", "1") != "0"]
-_defer_stats = {"queued": 0, "flushes": 0}
+_defer_stats = {"queued": 0, "flushes": 0, "norms_queued": 0, "norm_flushes": 0}
 
 
 class _TaskQueue:
     """queued weight-gradient problems of one graph task"""
-    __slots__ = ("entries", "__weakref__")
+    __slots__ = ("entries", "norms", "__weakref__")
 
     def __init__(self):
-        self.entries = []
+        self.entries = []  # node-row linears: (w, b, x, dy, spec, fused_b, alias of dw, alias of db)
+        self.norms = []    # layer norms: (weight, bias, x, dy, rstd, mean0, layout, alias of dw, alias of db)
 
 
 _task_queues = weakref.WeakValueDictionary()  # graph task id -> _TaskQueue (kept alive by that task's engine callback only)
@@ -626,11 +633,13 @@ def set_deferred_weight_gradients(on):
 
 
 def deferred_weight_gradient_stats(reset=False):
-    """{"queued": problems queued, "flushes": grouped launches} since the last reset: lets a caller (bench.py, the tests) state
-    whether the deferred path actually ran"""
-    out = dict(_defer_stats)
+    """{"queued": problems queued, "flushes": grouped launches} of the node-row linears since the last reset: lets a caller
+    (bench.py, the tests) state whether the deferred path actually ran.  "norms_queued" / "norm_flushes", the same for the layer
+    norms' affine gradients, appear once a norm has been queued."""
+    out = {k: v for k, v in _defer_stats.items() if not k.startswith("norm") or _defer_stats["norms_queued"]}
     if reset:
-        _defer_stats["queued"] = _defer_stats["flushes"] = 0
+        for k in _defer_stats:
+            _defer_stats[k] = 0
     return out
 
 
@@ -674,6 +683,41 @@ def _launch_queue(q, early=False):
     if descs:
         _defer_stats["flushes"] += 1
         _gemm_group(descs, _stream())
+    _launch_norm_queue(q, early)
+
+
+def _grad_target(p, a):
+    """where a queued gradient of parameter p lives now: the zero tensor backward() returned (alias a), unless AccumulateGrad
+    made a copy of it or summed several contributions -- then .grad is another tensor and receives the launch"""
+    t = _from_alias(a)
+    if p.grad is not None and p.grad.data_ptr() != t.data_ptr():
+        t = p.grad.view(-1)
+    if not t.is_contiguous() or t.dtype != torch.float32:
+        raise RuntimeError("deferred weight gradient: .grad must be a contiguous fp32 tensor")
+    return t
+
+
+def _ln_wgrad_group(descs, st):
+    """ONE grouped launch (eqf_layernorm_wgrad_group splits above its per-launch cap) of (x, dy, rstd, mean0, layout, dw, db)"""
+    arr = (EqfLnWgradDesc * len(descs))()
+    for d, (x, dy, rstd, mean0, layout, dw, db) in zip(arr, descs):
+        d.x, d.dy, d.rstd, d.mean0, d.d_weight, d.d_bias = _p(x), _p(dy), _p(rstd), _p(mean0), _p(dw), _p(db)
+        d.rows, d.irreps = x.shape[0], ctypes.pointer(layout.c)
+    call("eqf_layernorm_wgrad_group", arr, len(descs), st)
+
+
+def _launch_norm_queue(q, early):
+    """The layer norms' affine gradients of the pass, by the rules of the linear entries above: an early flush launches only
+    the entries whose weight AND bias have been accumulated; two norms that share a parameter both accumulate into its .grad."""
+    entries, q.norms = q.norms, []
+    if early:
+        q.norms = [e for e in entries if e[0].grad is None or e[1].grad is None]
+        entries = [e for e in entries if e[0].grad is not None and e[1].grad is not None]
+    descs = [(x, dy, rstd, mean0, layout, _grad_target(w, aw), _grad_target(b, ab))
+             for (w, b, x, dy, rstd, mean0, layout, aw, ab) in entries]
+    if descs:
+        _defer_stats["norm_flushes"] += 1
+        _ln_wgrad_group(descs, _stream())
 
 
 def flush_deferred_weight_gradients():
@@ -684,7 +728,7 @@ def flush_deferred_weight_gradients():
     except Exception:
         return
     q = _task_queues.get(task)
-    if q is not None and q.entries:
+    if q is not None and (q.entries or q.norms):
         _launch_queue(q, early=True)
 
 
@@ -720,7 +764,8 @@ def _can_defer(*params):
                     for p in params))
 
 
-def _defer_lin_wgrad(w, b, x, dy, spec, fused_b, dw, db):
+def _task_queue():
+    """the queue of the current graph task, created (with its engine callback) on first use"""
     task = torch._C._current_graph_task_id()
     q = _task_queues.get(task)
     if q is None:
@@ -728,8 +773,20 @@ def _defer_lin_wgrad(w, b, x, dy, spec, fused_b, dw, db):
         _task_queues[task] = q
         # the closure is the ONLY strong reference to the queue: it lives exactly as long as the graph task does
         torch.autograd.Variable._execution_engine.queue_callback(lambda q=q: _launch_queue(q))
-    q.entries.append((w, b, x, dy, spec, fused_b, _alias(dw), _alias(db) if fused_b else None))
+    return q
+
+
+def _defer_lin_wgrad(w, b, x, dy, spec, fused_b, dw, db):
+    _task_queue().entries.append((w, b, x, dy, spec, fused_b, _alias(dw), _alias(db) if fused_b else None))
     _defer_stats["queued"] += 1
+
+
+def _defer_norm_wgrad(weight, bias, x, dy, rstd, mean0, layout, dw, db):
+    """The affine gradients of a layer norm are parameter gradients only: like the linears' weight gradients they are queued
+    during loss.backward() and launched in ONE group when the pass ends (13 launches of 72 workgroups, each as long as its
+    64-row latency chain, become one of 936).  The entry keeps x, dy, rstd and mean0 alive until then."""
+    _task_queue().norms.append((weight, bias, x, dy, rstd, mean0, layout, _alias(dw), _alias(db)))
+    _defer_stats["norms_queued"] += 1
 
 
 def _launch(built):
@@ -1555,6 +1612,11 @@ def _gather_add_bwd(dmsg, g, n, want_a, want_b):
     D = dmsg.shape[1]
     st = _stream()
     da = db = None
+    if want_a and want_b:  # both adjoints read the same dmsg: one launch
+        da = torch.empty((n, D), device=dmsg.device, dtype=torch.float32)
+        db = torch.empty((n, D), device=dmsg.device, dtype=torch.float32)
+        call("eqf_segment_sum_pair", _p(dmsg), _p(g.src_ptr), _p(g.src_perm), _p(da), _p(g.row_ptr), None, _p(db), n, D, st)
+        return da, db
     if want_a:
         da = torch.empty((n, D), device=dmsg.device, dtype=torch.float32)
         call("eqf_segment_sum", _p(dmsg), _p(g.src_ptr), _p(g.src_perm), _p(da), n, D, 1.0, 0, st)

@@ -377,6 +377,18 @@ int eqf_layernorm_bwd(const float* x, const float* weight, const float* dy, cons
                       const float* mean0, float* dx, float* d_weight, float* d_bias, int rows,
                       const eqf_irreps* irreps, void* stream);
 
+/* The affine gradients of n norms in grouped launches: d_weight / d_bias of problem i ACCUMULATED from its x (the normalised
+ * input), dy, rstd and mean0 exactly as eqf_layernorm_bwd does (the same per-thread partial sums; only the order of the
+ * atomics differs).  Two problems may name the same accumulators.  A problem with rows <= 0 is skipped.  One launch takes up
+ * to 32 problems with up to 4 distinct row layouts; beyond either the group is split into several launches. */
+typedef struct eqf_ln_wgrad_desc {
+  const float *x, *dy, *rstd, *mean0;
+  float *d_weight, *d_bias;
+  int rows;
+  const eqf_irreps* irreps;
+} eqf_ln_wgrad_desc;
+int eqf_layernorm_wgrad_group(const eqf_ln_wgrad_desc* descs, int n, void* stream);
+
 /* The same with the residual add in front of the norm folded in [ref: TransBlock.forward, nets/graph_attention_transformer.py:
  * 639-667: node_output = node_input + ga(...); ffn(norm_2(node_output)) ...]: xsum = x + x2 is written and normalised in one
  * pass (x2 == xsum == NULL: plain layer norm).  bwd: dx = LN'(dy) + dres (dres = gradient arriving at xsum from the
@@ -474,6 +486,11 @@ int eqf_gather_add_fwd(const float* a, const float* b, const int* src, const int
  * [ref: torch_scatter.scatter call sites, nets/graph_attention_transformer.py:513,700] */
 int eqf_segment_sum(const float* x, const int* ptr, const int* perm, float* out, int nseg, int D,
                     float scale, int accumulate, void* stream);
+/* Two segmented sums of the SAME x in one launch (both adjoints of eqf_gather_add_fwd): out_a as eqf_segment_sum(x, ptr_a,
+ * perm_a, out_a, nseg, D, 1, 0), out_b likewise; each segment is summed in the same order, so both outputs are bit-equal to
+ * those of the two single launches.  perm_a / perm_b may be NULL. */
+int eqf_segment_sum_pair(const float* x, const int* ptr_a, const int* perm_a, float* out_a, const int* ptr_b,
+                         const int* perm_b, float* out_b, int nseg, int D, void* stream);
 /* out[q,:] = scale * x[seg_of[q],:]  (row broadcast: backward of eqf_segment_sum with perm == NULL). */
 int eqf_segment_bcast(const float* x, const int* seg_of, float* out, int rows, int D, float scale,
                       void* stream);
