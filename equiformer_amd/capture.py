@@ -147,7 +147,101 @@ class PaddedBatch:
     `model(view, graph=graph, offsets=view.offsets)` with "tags" among the node targets."""
 
 
-class BucketedTrainStep:
+class _BucketedStep:
+    """What BucketedTrainStep and equiformer_amd.evaluate.BucketedEvalStep share: the bucket records with their LRU order and
+    counters, the padded view of a bucket's graph, its target buffers, and the first half of a step (the plan of the batch's
+    radius graph -- the one host read-back -- and its bucket key)."""
+
+    def _init_buckets(self, radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors):
+        import collections
+        self.radius, self.max_num_neighbors = float(radius), int(max_num_neighbors)
+        self.graph_targets, self.node_targets = tuple(graph_targets), tuple(node_targets)
+        self.min_eager, self.max_graphs = int(min_eager), max(1, int(max_graphs))
+        self.node_step, self.edge_step = int(node_step), int(edge_step)
+        self._graphs = collections.OrderedDict()  # bucket key -> the record of a captured bucket, least recently used first
+        self._seen = collections.OrderedDict()    # bucket key -> eager steps so far (counts only, at most _SEEN_MAX keys)
+        self.replays = self.eager_steps = self.captures = self.evictions = 0
+        self.real_edges = self.padded_edges = self.real_nodes = self.padded_nodes = 0
+        self.captures_of = {}  # bucket key -> captures (a key captured twice was evicted in between)
+        self._periodic = None  # set by the first batch
+
+    def live_graphs(self):
+        return list(self._graphs)
+
+    def _view(self, g, B):
+        v = PaddedBatch()
+        # (detached aliases: a model that marks `pos` as requiring grad -- the MD17 force pass -- must not mark the graph's buffer)
+        v.pos, v.z, v.batch = g.pos.detach(), g.z, g.batch
+        v.node_mask, v.graph_mask, v.B = g.node_mask, g.graph_mask, B
+        if getattr(g, "_pbc", False):
+            v.offsets, v.cell_offsets, v.atomic_numbers = g.offsets, g.cell_offsets, g.z
+        return v
+
+    def _fill_targets(self, view, batch, g, B, fresh):
+        with torch.no_grad():
+            for names, rows, real in ((self.graph_targets, B + 1, B), (self.node_targets, g.N, g.n_real)):
+                for name in names:
+                    t = batch[name]
+                    if t.shape[0] != real:
+                        raise ValueError("target %r has %d rows, the batch has %d" % (name, t.shape[0], real))
+                    if fresh:
+                        setattr(view, name, torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=g.src.device))
+                    buf = getattr(view, name)
+                    buf[:real].copy_(t, non_blocking=True)
+                    if not fresh:
+                        buf[real:].zero_()
+
+    def _plan(self, batch):
+        """(B, z, plan, build, key) of a batch: the graph plan (its host read-back happens here) and the bucket it falls into"""
+        from .graph import EdgeGraph
+        b = batch["batch"]
+        B = int(batch["num_graphs"]) if "num_graphs" in batch else int(b[-1].item()) + 1
+        z = batch["z"] if "z" in batch else batch.get("atomic_numbers")
+        if self._periodic:
+            plan = EdgeGraph.radius_pbc_plan(batch["pos"], batch["cell"], b, self.radius, self.max_num_neighbors, B)
+            build = EdgeGraph.from_radius_pbc_plan
+        else:
+            plan = EdgeGraph.radius_plan(batch["pos"], b, self.radius, self.max_num_neighbors, B)
+            build = EdgeGraph.from_radius_plan
+        key = bucket_of(B, plan.N, plan.E, self.node_step, self.edge_step)
+        self.real_nodes += plan.N
+        self.real_edges += plan.E
+        self.padded_nodes += key[1]
+        self.padded_edges += key[2]
+        return B, z, plan, build, key
+
+    def _check_periodic(self, batch):
+        periodic = "cell" in batch
+        if self._periodic is None:
+            self._periodic = periodic
+        elif self._periodic != periodic:
+            raise ValueError("%s: one instance serves periodic or non-periodic batches, not both" % type(self).__name__)
+
+    def _count_eager(self, key):
+        """True while the bucket `key` still runs eagerly (its first `min_eager` steps); counts the step then"""
+        n = self._seen.get(key, 0)
+        if n >= self.min_eager:
+            return False
+        self._seen[key] = n + 1
+        self._seen.move_to_end(key)
+        while len(self._seen) > _SEEN_MAX:
+            self._seen.popitem(last=False)
+        self.eager_steps += 1
+        return True
+
+    def _make_room(self):
+        while len(self._graphs) >= self.max_graphs:  # least recently used out; its bucket earns a graph again
+            old, _ = self._graphs.popitem(last=False)
+            self._seen.pop(old, None)
+            self.evictions += 1
+
+    def _captured(self, key, rec):
+        self._graphs[key] = rec
+        self.captures += 1
+        self.captures_of[key] = self.captures_of.get(key, 0) + 1
+
+
+class BucketedTrainStep(_BucketedStep):
     """bs = BucketedTrainStep(optimizer, forward_loss, radius, graph_targets=("y",), node_targets=())
        loss = bs.step(batch)        # batch: mapping with pos [N, 3], z [N], batch [N] (ascending) and the targets; N, E vary
 
@@ -174,24 +268,11 @@ class BucketedTrainStep:
                  node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000):
         if getattr(optimizer, "_reducer", None) is not None:
             raise ValueError("BucketedTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
-        import collections
         self.opt, self.forward_loss = optimizer, forward_loss
-        self.radius, self.max_num_neighbors = float(radius), int(max_num_neighbors)
-        self.graph_targets, self.node_targets = tuple(graph_targets), tuple(node_targets)
-        self.min_eager, self.max_graphs = int(min_eager), max(1, int(max_graphs))
-        self.node_step, self.edge_step = int(node_step), int(edge_step)
-        self._graphs = collections.OrderedDict()  # bucket key -> dict(graph, sg, view, loss), least recently used first
-        self._seen = collections.OrderedDict()    # bucket key -> eager steps so far (counts only, at most _SEEN_MAX keys)
+        self._init_buckets(radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors)
         dev = optimizer.flat_p.device
         self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-        self.replays = self.eager_steps = self.captures = self.evictions = 0
-        self.real_edges = self.padded_edges = self.real_nodes = self.padded_nodes = 0
-        self.captures_of = {}  # bucket key -> captures (a key captured twice was evicted in between)
-        self._periodic = None  # set by the first batch
-
-    def live_graphs(self):
-        return list(self._graphs)
 
     def _run(self, g, view):
         self.opt.zero_grad(set_to_none=True)
@@ -204,51 +285,10 @@ class BucketedTrainStep:
         self._seed_host[0] = int(torch.randint(0, 2 ** 62, (1,)).item())
         self._seed_dev.copy_(self._seed_host, non_blocking=True)
 
-    def _view(self, g, B):
-        v = PaddedBatch()
-        # (detached aliases: a model that marks `pos` as requiring grad -- the MD17 force pass -- must not mark the graph's buffer)
-        v.pos, v.z, v.batch = g.pos.detach(), g.z, g.batch
-        v.node_mask, v.graph_mask, v.B = g.node_mask, g.graph_mask, B
-        if getattr(g, "_pbc", False):
-            v.offsets, v.cell_offsets, v.atomic_numbers = g.offsets, g.cell_offsets, g.z
-        return v
-
-    def _fill_targets(self, view, batch, g, B, fresh):
-        with torch.no_grad():
-            for names, rows, real in ((self.graph_targets, B + 1, B), (self.node_targets, g.N, g.n_real)):
-                for name in names:
-                    t = batch[name]
-                    if t.shape[0] != real:
-                        raise ValueError("target %r has %d rows, the batch has %d" % (name, t.shape[0], real))
-                    if fresh:
-                        setattr(view, name, torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=g.src.device))
-                    buf = getattr(view, name)
-                    buf[:real].copy_(t, non_blocking=True)
-                    if not fresh:
-                        buf[real:].zero_()
-
     def step(self, batch):
-        from .graph import EdgeGraph
-        periodic = "cell" in batch
-        if self._periodic is None:
-            self._periodic = periodic
-        elif self._periodic != periodic:
-            raise ValueError("BucketedTrainStep: one instance serves periodic or non-periodic batches, not both")
-        b = batch["batch"]
-        B = int(batch["num_graphs"]) if "num_graphs" in batch else int(b[-1].item()) + 1
-        z = batch["z"] if "z" in batch else batch.get("atomic_numbers")
+        self._check_periodic(batch)
         self._draw_seed()  # (the device word goes out BEFORE the graph build's host read-back: it overlaps it)
-        if periodic:
-            plan = EdgeGraph.radius_pbc_plan(batch["pos"], batch["cell"], b, self.radius, self.max_num_neighbors, B)
-            build = EdgeGraph.from_radius_pbc_plan
-        else:
-            plan = EdgeGraph.radius_plan(batch["pos"], b, self.radius, self.max_num_neighbors, B)
-            build = EdgeGraph.from_radius_plan
-        key = bucket_of(B, plan.N, plan.E, self.node_step, self.edge_step)
-        self.real_nodes += plan.N
-        self.real_edges += plan.E
-        self.padded_nodes += key[1]
-        self.padded_edges += key[2]
+        B, z, plan, build, key = self._plan(batch)
         rec = self._graphs.get(key)
         if rec is not None:
             self._graphs.move_to_end(key)
@@ -261,18 +301,9 @@ class BucketedTrainStep:
         g = build(plan, key[1:], z=z)
         view = self._view(g, B)
         self._fill_targets(view, batch, g, B, fresh=True)
-        n = self._seen.get(key, 0)
-        if n < self.min_eager:
-            self._seen[key] = n + 1
-            self._seen.move_to_end(key)
-            while len(self._seen) > _SEEN_MAX:
-                self._seen.popitem(last=False)
-            self.eager_steps += 1
+        if self._count_eager(key):
             return self._run(g, view)
-        while len(self._graphs) >= self.max_graphs:  # least recently used out; its bucket earns a graph again
-            old, _ = self._graphs.popitem(last=False)
-            self._seen.pop(old, None)
-            self.evictions += 1
+        self._make_room()
         # capture this bucket: the launches record the addresses of g's tensors, of the view's buffers and of the gradients /
         # activations the graph's private pool hands out; they see N_cap, E_cap and B + 1 only
         self.opt.device_hyper(True)
@@ -282,9 +313,7 @@ class BucketedTrainStep:
             with torch.cuda.graph(graph):
                 loss = self._run(g, view)
             self.opt._step = step_before  # (capturing enqueued nothing: the step count advances with the replays)
-        self._graphs[key] = dict(graph=graph, sg=g, view=view, loss=loss)
-        self.captures += 1
-        self.captures_of[key] = self.captures_of.get(key, 0) + 1
+        self._captured(key, dict(graph=graph, sg=g, view=view, loss=loss))
         self._draw_seed()
         self.opt.advance_captured()
         graph.replay()

@@ -1945,6 +1945,39 @@ def dens_loss(pred_y, pred_dy, y, dy, noise_vec, noise_mask, weights, task_mean,
                            noise_std)
 
 
+METRICS_SUMS = 10        # EQF_METRICS_SUMS of include/equiformer_hip.h
+METRICS_THREADS = 256    # EQF_METRICS_THREADS: the workgroup of eqf_metrics_accumulate
+
+
+def metrics_accumulate(acc, pred_y, y, n_graphs, task_mean, task_std, threshold, pred_dy=None, dy=None, node_mask=None):
+    """acc [10] fp64 += the metric sums of one batch (include/equiformer_hip.h eqf_metrics_accumulate) [ref: engine.py:136-139,
+    main_md17.py:451-462, energy_trainer_v2.py:445-459]: one launch, no gradient, nothing read back.  pred_y (normalised) / y
+    (real units): fp32 with at least n_graphs elements, of which the first n_graphs count; pred_dy / dy [N, 3] fp32 and
+    node_mask [N] fp32 (1 real / 0 phantom) are optional."""
+    if not acc.is_cuda:
+        raise HipOnlyError("the Equiformer hot path runs on MI355X only (got a %s tensor); there is no CPU fallback" % acc.device)
+    pred_y, y = pred_y.detach(), y.detach()
+    _chk(pred_y, y, pred_dy, dy, node_mask)
+    n_graphs = int(n_graphs)
+    if acc.dtype != torch.float64 or acc.numel() != METRICS_SUMS or not acc.is_contiguous():
+        raise ValueError("acc: %d contiguous fp64 device words" % METRICS_SUMS)
+    if n_graphs < 0 or pred_y.numel() < n_graphs or y.numel() < n_graphs:
+        raise ValueError("metrics_accumulate: pred_y %s, y %s, n_graphs %d" % (tuple(pred_y.shape), tuple(y.shape), n_graphs))
+    N = 0
+    if pred_dy is not None:
+        if dy is None:
+            raise ValueError("metrics_accumulate: pred_dy without dy")
+        pred_dy, dy = pred_dy.detach(), dy.detach()
+        N = pred_dy.shape[0]
+        if tuple(pred_dy.shape) != (N, 3) or tuple(dy.shape) != (N, 3) or (node_mask is not None and node_mask.numel() != N):
+            raise ValueError("metrics_accumulate: pred_dy %s, dy %s, node_mask %s" % (
+                tuple(pred_dy.shape), tuple(dy.shape), None if node_mask is None else tuple(node_mask.shape)))
+    else:
+        dy = node_mask = None
+    call("eqf_metrics_accumulate", _p(pred_y), _p(y), n_graphs, _p(pred_dy), _p(dy), _p(node_mask), N, float(task_mean),
+         float(task_std), float(threshold), ctypes.c_void_p(acc.data_ptr()), _stream())
+
+
 class _RbfGaussian(Function):
     @staticmethod
     def forward(ctx, length, mean, std, weight, bias, cutoff):

@@ -701,6 +701,31 @@ int eqf_dens_loss_bwd(const float* d_loss, const float* pred_y, const float* y, 
                       const float* stats, int N, int nB, double task_mean, double task_std, double noise_std,
                       float* d_pred_y, float* d_pred_dy, void* stream);
 
+/* Running evaluation metrics, one launch per batch.  [ref: engine.py:136-139 evaluate (L1 loss and MAE meters),
+ * main_md17.py:451-462 evaluate (energy / force loss and MAE meters), the OC20 trainer's _compute_metrics
+ * (energy_trainer_v2.py:445-459: energy_mae, energy_mse, energy_within_threshold) -- each a `.item()` read-back per batch]
+ * With t = (y - task_mean) / task_std and e = pred_y task_std + task_mean - y over the first n_graphs rows, and over the
+ * rows i < N whose node_mask is not 0 (node_mask NULL: every row), the launch ADDS to acc[EQF_METRICS_SUMS]:
+ *   acc[0] += n_graphs                       acc[5] += rows counted (atoms)
+ *   acc[1] += sum |pred_y - t|               acc[6] += sum_i ||pred_dy[i] - dy[i] / task_std||_2
+ *   acc[2] += sum |e|                        acc[7] += sum_ic |pred_dy[i,c] - dy[i,c] / task_std|
+ *   acc[3] += sum e^2                        acc[8] += sum_ic |pred_dy[i,c] task_std - dy[i,c]|
+ *   acc[4] += #{|e| < threshold}             acc[9] += sum_ic (pred_dy[i,c] task_std - dy[i,c])^2
+ * pred_y (normalised) and y (real units) hold at least n_graphs floats; pred_dy / dy are [N, 3].  pred_dy == NULL or
+ * N == 0 skips the force terms (acc[5..9] get +0); pred_dy without dy is an argument error, as are a missing pred_y, y
+ * or acc, task_std <= 0 and negative counts -- all refused before anything is launched.  Rows >= n_graphs and rows whose
+ * mask is 0 are never read: a NaN or Inf there leaves every sum untouched.  fp64 arithmetic from the fp32 inputs; one
+ * workgroup of EQF_METRICS_THREADS lanes, lane-strided partial sums combined in a fixed order, one thread adds the batch
+ * total into acc: no atomics, no workspace, the same bits on every run.  Enqueue-only (no allocation, no
+ * synchronisation): legal inside a stream capture.  Launches that share `acc` must be ordered, i.e. on ONE stream (or
+ * replays of graphs launched on one stream); that is the only concurrency supported.  Clear acc with a memset on that
+ * stream. */
+#define EQF_METRICS_SUMS 10
+#define EQF_METRICS_THREADS 256
+int eqf_metrics_accumulate(const float* pred_y, const float* y, int n_graphs, const float* pred_dy, const float* dy,
+                           const float* node_mask, int N, double task_mean, double task_std, double threshold, double* acc,
+                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; used by bench.py for the roofline line)
  * ------------------------------------------------------------------------------------------- */
