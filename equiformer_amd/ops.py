@@ -99,10 +99,16 @@ class matrix_mode:
 
 def _guard(t, dep, what):
     """First-order parameter gradient handed out by a create_graph backward: usable as a value, raises when something
-    tries to differentiate through it (second derivatives wrt parameters-of-parameters are not implemented)."""
+    tries to differentiate through it (second derivatives wrt parameters-of-parameters are not implemented).
+    dep: the tensors the gradient is a function of -- the output cotangent AND the operator's differentiable inputs (a weight
+    gradient is bilinear in the two).  Every one of them that is part of a graph becomes an input of the guard, so that a
+    backward pass reaches the guard by whichever of them it differentiates.  Guarding on the cotangent alone handed the gradient
+    out as a constant when the cotangent was one and the input was not, and let a pass that only asked for the derivative wrt
+    the input walk past the guard: either way a term silently missing (tests/test_gpu_second_order_ops.py::test_guard_*)."""
     if t is None:
         return None
-    return _Guard.apply(t, dep, what) if dep.requires_grad else t
+    deps = [d for d in (dep if isinstance(dep, (tuple, list)) else (dep,)) if d is not None and d.requires_grad]
+    return _Guard.apply(t, what, *deps) if deps else t
 
 
 def _nonnull(t):
@@ -258,7 +264,7 @@ class _LayerNorm(Function):
         x, weight, rstd, mean0, bias = ctx.saved_tensors
         if torch.is_grad_enabled():  # create_graph: the backward is itself a differentiable HIP operator
             dx, dw, db = _LayerNormBwd.apply(x, weight, dy, rstd, mean0, ctx.layout, ctx.eps, ctx.nb)
-            return dx, _guard(dw, dy, "layer-norm weight gradient"), _guard(db, dy, "layer-norm bias gradient"), \
+            return dx, _guard(dw, (dy, x), "layer-norm weight gradient"), _guard(db, dy, "layer-norm bias gradient"), \
                 None, None
         dy = _c(dy)
         _chk(dy)
@@ -327,17 +333,20 @@ class _AddLayerNorm(Function):
              layout.c_ref, float(eps), _stream())
         ctx.save_for_backward(s, weight, rstd, mean0, bias)
         ctx.layout, ctx.nb, ctx.eps = layout, bias.numel(), eps
+        # an output nothing was derived from arrives in backward as None, not as a tensor of zeros autograd made for it: the
+        # branches on `dy is None` / `ds is None` below are taken only with this
+        ctx.set_materialize_grads(False)
         return s, y
 
     @staticmethod
     def backward(ctx, ds, dy):
         s, weight, rstd, mean0, bias = ctx.saved_tensors
-        if dy is None:  # the normalised branch is unused: identity on the sum
+        if dy is None:  # the normalised branch is unused: identity on the sum, no launch
             return ds, ds, None, None, None, None
         if torch.is_grad_enabled():  # create_graph: differentiable norm backward + a differentiable add
             dx, dw, db = _LayerNormBwd.apply(s, weight, dy, rstd, mean0, ctx.layout, ctx.eps, ctx.nb)
             d = dx if ds is None else dx + ds
-            return d, d, _guard(dw, dy, "layer-norm weight gradient"), _guard(db, dy, "layer-norm bias gradient"), \
+            return d, d, _guard(dw, (dy, s), "layer-norm weight gradient"), _guard(db, dy, "layer-norm bias gradient"), \
                 None, None
         dy = _c(dy)
         ds = _c(ds) if ds is not None else None
@@ -419,7 +428,7 @@ class _GraphNorm(Function):
         dx, dms, dw, db = _gn_bwd(x, mean_shift, weight, dy, None, mean, rstd, ctx.graph, ctx.layout, ctx.nb,
                                   _want_param_grads())
         if torch.is_grad_enabled():
-            dx, dms, dw, db = (_guard(t, dy, "graph norm") for t in (dx, dms, dw, db))
+            dx, dms, dw, db = (_guard(t, (dy, x, mean_shift, weight), "graph norm") for t in (dx, dms, dw, db))
         return dx, dms, dw, db, None, None, None
 
 
@@ -448,8 +457,7 @@ class _AddGraphNorm(Function):
         d, dms, dw, db = _gn_bwd(s, mean_shift, weight, dy, ds, mean, rstd, ctx.graph, ctx.layout, ctx.nb,
                                  _want_param_grads())
         if torch.is_grad_enabled():
-            dep = dy if (ds is None or dy.requires_grad) else ds
-            d, dms, dw, db = (_guard(t, dep, "graph norm") for t in (d, dms, dw, db))
+            d, dms, dw, db = (_guard(t, (dy, ds, s, mean_shift, weight), "graph norm") for t in (d, dms, dw, db))
         return d, d, dms, dw, db, None, None, None
 
 
@@ -1194,7 +1202,8 @@ class _LnSilu(Function):
         G = ctx.groups
         if torch.is_grad_enabled():  # create_graph
             dx, dg, db = _LnSiluBwd.apply(x, gamma, beta, dy, ctx.eps, G)
-            return dx, _guard(dg, dy, "LayerNorm weight gradient"), _guard(db, dy, "LayerNorm bias gradient"), \
+            return dx, _guard(dg, (dy, x, gamma, beta), "LayerNorm weight gradient"), \
+                _guard(db, (dy, x, gamma, beta), "LayerNorm bias gradient"), \
                 None, None
         dy = _c(dy)
         _chk(dy)
@@ -1995,7 +2004,7 @@ class _RbfGaussian(Function):
         length, mean, std, weight, bias = ctx.saved_tensors
         if torch.is_grad_enabled() and ctx.needs_input_grad[0]:  # create_graph (forces of a gaussian-basis MD17 model)
             outs = _RbfGaussianBwd.apply(length, mean, std, weight, bias, dout, ctx.cutoff)
-            return (outs[0],) + tuple(_guard(t, dout, "radial-basis parameter gradient") for t in outs[1:]) + (None,)
+            return (outs[0],) + tuple(_guard(t, (dout, length, mean, std, weight, bias), "radial-basis parameter gradient") for t in outs[1:]) + (None,)
         dout = _c(dout)
         _chk(dout)
         return _rbf_gaussian_bwd(length, mean, std, weight, bias, dout, ctx.cutoff, ctx.needs_input_grad[0]) + (None,)
@@ -2145,7 +2154,7 @@ class _RbfBessel(Function):
         length, freq = ctx.saved_tensors
         if torch.is_grad_enabled() and ctx.needs_input_grad[0]:  # create_graph
             dlen, dfreq = _RbfBesselBwd.apply(length, freq, dout, ctx.cutoff)
-            return dlen, _guard(dfreq, dout, "Bessel frequency gradient"), None
+            return dlen, _guard(dfreq, (dout, length, freq), "Bessel frequency gradient"), None
         dout = _c(dout)
         _chk(dout)
         dlen = torch.empty_like(length) if ctx.needs_input_grad[0] else None
@@ -2505,7 +2514,7 @@ class _Guard(Function):
     """Identity whose backward raises: marks a first-order result that must not be differentiated again."""
 
     @staticmethod
-    def forward(ctx, t, dep, what):
+    def forward(ctx, t, what, *deps):  # deps: what t was computed from; they only tie the result to their graphs
         ctx.what = what
         return t.view_as(t)
 
@@ -2721,8 +2730,9 @@ class _SepFctp(Function):
                     gW_ = _zeros_like(weight)
                     gW2_ = _zeros_like(weight2) if weight2 is not None else None
                     _sfc_bwd_weight(x, coupling, w, _c(d1), _c(d2) if spec.n2 else None, spec, gW_, gW2_, ctx.mode)
-                gW = _guard(gW_, d1, "weight gradient of the fused SeparableFCTP")
-                gW2 = _guard(gW2_, d1, "weight gradient of the fused SeparableFCTP") if gW2_ is not None else None
+                deps = (d1, d2, x, coupling, w)
+                gW = _guard(gW_, deps, "weight gradient of the fused SeparableFCTP")
+                gW2 = _guard(gW2_, deps, "weight gradient of the fused SeparableFCTP") if gW2_ is not None else None
             if ctx.has_bias[0] and need[4]:
                 j = spec.out_layout.seg_index(0)
                 o = spec.out_layout.offsets[j]
@@ -2831,7 +2841,7 @@ class _SepFctpGated(Function):
                 with torch.no_grad():
                     gW_ = _zeros_like(weight)
                     _sfc_bwd_weight(xg.detach(), coupling, w, _c(d1), None, spec, gW_, None, mode)
-                gW = _guard(gW_, d1, "weight gradient of the fused SeparableFCTP")
+                gW = _guard(gW_, (d1, x_raw, coupling, w), "weight gradient of the fused SeparableFCTP")
             if ctx.has_bias and need[4]:
                 o = spec.out_layout.offsets[spec.out_layout.seg_index(0)]
                 gb = d1[:, o:o + spec.out_layout.mul_of(0)].sum(0)
@@ -2913,7 +2923,7 @@ class _AlphaLogits(Function):
         H, Kh, c = ctx.args
         if torch.is_grad_enabled():  # create_graph
             da, dd = _AlphaLogitsBwd.apply(a, alpha_dot, dlogit, H, Kh, c)
-            return da, _guard(dd, dlogit, "alpha_dot gradient"), None, None, None
+            return da, _guard(dd, (dlogit, a), "alpha_dot gradient"), None, None, None
         dlogit = _c(dlogit)
         _chk(dlogit)
         da = torch.empty_like(a)

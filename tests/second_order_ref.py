@@ -11,6 +11,7 @@ the create_graph path; nothing under equiformer_amd/ imports it any more.
 
 Formulas restate the same reference code as the HIP kernels they shadow (cited per function).
 """
+import contextlib
 import math
 
 import torch
@@ -28,6 +29,79 @@ def vjp(fn, inputs, grad_outputs):
                                     allow_unused=True)
     it = iter(grads)
     return [next(it) if (torch.is_tensor(t) and t.requires_grad) else None for t in inputs]
+
+
+# ------------------------------------------------------------------------------------------------- comparison scheme
+# For an operator y = f(x; theta):  L = sum_k <b_k, d<a, f(x; theta)> / d x_k>  over the inputs x_k of `diff` is a scalar
+# whose gradient wrt every differentiable input and wrt the cotangent a is what `loss.backward()` asks of the operator when
+# forces were taken with create_graph=True.  tests/test_gpu_second_order.py and tests/test_gpu_second_order_ops.py run the
+# HIP operator (fp32, device) and the restatement (fp64, CPU) through the same expression and compare.
+TOL = 2e-5  # of the largest entry: fp32 kernels, sums over rows
+
+
+def _dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+def _rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+
+
+def _second_order(fn, inputs, diff, seed, first_ctx=None, use=None, drop=None):
+    """inputs: list of tensors; diff: indices of the inputs the FIRST derivative is taken with respect to.
+    Returns (first derivatives, gradients of L = sum_k <b_k, d<a, f>/d x_k> wrt every input and wrt a).
+    first_ctx: factory of a context manager that wraps the first-derivative call (ops.input_grads_only);
+    use: indices of the outputs whose cotangent takes part (default: all of them);
+    drop: position in `diff` of a first derivative that is detached before L is formed, i.e. whose cotangent b_k the double
+    backward never sees (the negative controls of tests/test_tp_restatements.py: a composition that forgot that term)."""
+    outs = fn(*inputs)
+    outs = list(outs) if isinstance(outs, (tuple, list)) else [outs]
+    g = torch.Generator().manual_seed(seed)
+    a = [torch.randn(o.shape, generator=g, dtype=torch.float64).to(o.dtype).to(o.device).requires_grad_(True) for o in outs]
+    if use is not None:
+        outs, a = [outs[i] for i in use], [a[i] for i in use]
+    with (first_ctx() if first_ctx is not None else contextlib.nullcontext()):
+        first = torch.autograd.grad(outs, [inputs[i] for i in diff], a, create_graph=True)
+    b = [torch.randn(f.shape, generator=g, dtype=torch.float64).to(f.dtype).to(f.device) for f in first]
+    L = sum((bb * (ff.detach() if k == drop else ff)).sum() for k, (bb, ff) in enumerate(zip(b, first)))
+    wrt = [t for t in inputs if t.requires_grad] + a
+    second = torch.autograd.grad(L, wrt, allow_unused=True)
+    return first, second
+
+
+def _compare(fn_hip, fn_ref, inputs64, diff, seed, params=(), tol=None, first_ctx=None, use=None, record=None, ref=None):
+    """inputs64: fp64 CPU tensors (requires_grad set by the caller).
+    tol: bar of this call (default TOL), a number or a function (kind, k) -> number with kind "first" / "second" and k the
+    index in the list of `_second_order`; first_ctx, use: see `_second_order` (the context wraps the HIP call only);
+    record: called with (kind, k, error) for every compared quantity before it is asserted;
+    ref: (dict, key) -- the fp64 result is computed once per key and shared by the calls that compare against it (the same
+    inputs, diff, seed and use in several arithmetic modes)."""
+    dev = _dev()
+    bar = (lambda kind, k: TOL if tol is None else tol) if not callable(tol) else tol
+    in_hip = [t.detach().float().to(dev).requires_grad_(t.requires_grad) for t in inputs64]
+    if ref is None or ref[1] not in ref[0]:
+        in_ref = [t.clone().requires_grad_(t.requires_grad) for t in inputs64]
+        f_ref, s_ref = _second_order(fn_ref, in_ref, diff, seed, None, use)
+        f_ref, s_ref = [t.detach() for t in f_ref], [None if t is None else t.detach() for t in s_ref]
+        if ref is not None:
+            ref[0][ref[1]] = (f_ref, s_ref)
+    else:
+        f_ref, s_ref = ref[0][ref[1]]
+    f_hip, s_hip = _second_order(fn_hip, in_hip, diff, seed, first_ctx, use)
+    for k, (x, r) in enumerate(zip(f_hip, f_ref)):
+        if record is not None:
+            record("first", k, _rel(x, r))
+        assert _rel(x, r) < bar("first", k), ("first", k, _rel(x, r))
+    for k, (x, r) in enumerate(zip(s_hip, s_ref)):
+        if r is None or float(r.abs().max()) == 0.0:
+            assert x is None or float(x.abs().max()) < 1e-6, ("second", k)
+            continue
+        assert x is not None, ("second", k)
+        if record is not None:
+            record("second", k, _rel(x, r))
+        assert _rel(x, r) < bar("second", k), ("second", k, _rel(x, r))
 
 
 # ------------------------------------------------------------------------------------------------- row-local ops

@@ -15,52 +15,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import second_order_ref as so  # noqa: E402
+from second_order_ref import TOL, _compare, _dev, _rel, _second_order  # noqa: E402,F401  (the comparison scheme)
 
 pytestmark = pytest.mark.gpu
-
-TOL = 2e-5
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-def _second_order(fn, inputs, diff, seed):
-    """inputs: list of tensors; diff: indices of the inputs the FIRST derivative is taken with respect to.
-    Returns (first derivatives, gradients of L = sum_k <b_k, d<a, f>/d x_k> wrt every input and wrt a)."""
-    outs = fn(*inputs)
-    outs = list(outs) if isinstance(outs, (tuple, list)) else [outs]
-    g = torch.Generator().manual_seed(seed)
-    a = [torch.randn(o.shape, generator=g, dtype=torch.float64).to(o.dtype).to(o.device).requires_grad_(True) for o in outs]
-    first = torch.autograd.grad(outs, [inputs[i] for i in diff], a, create_graph=True)
-    b = [torch.randn(f.shape, generator=g, dtype=torch.float64).to(f.dtype).to(f.device) for f in first]
-    L = sum((bb * ff).sum() for bb, ff in zip(b, first))
-    wrt = [t for t in inputs if t.requires_grad] + a
-    second = torch.autograd.grad(L, wrt, allow_unused=True)
-    return first, second
-
-
-def _compare(fn_hip, fn_ref, inputs64, diff, seed, params=()):
-    """inputs64: fp64 CPU tensors (requires_grad set by the caller)."""
-    dev = _dev()
-    in_ref = [t.clone().requires_grad_(t.requires_grad) for t in inputs64]
-    in_hip = [t.detach().float().to(dev).requires_grad_(t.requires_grad) for t in inputs64]
-    f_ref, s_ref = _second_order(fn_ref, in_ref, diff, seed)
-    f_hip, s_hip = _second_order(fn_hip, in_hip, diff, seed)
-    for k, (x, r) in enumerate(zip(f_hip, f_ref)):
-        assert _rel(x, r) < TOL, ("first", k, _rel(x, r))
-    for k, (x, r) in enumerate(zip(s_hip, s_ref)):
-        if r is None or float(r.abs().max()) == 0.0:
-            assert x is None or float(x.abs().max()) < 1e-6, ("second", k)
-            continue
-        assert x is not None, ("second", k)
-        assert _rel(x, r) < TOL, ("second", k, _rel(x, r))
 
 
 def _rows(n, d, seed, scale=1.0):
@@ -319,3 +276,233 @@ def test_edge_geometry_bwd2(lmax):
         return length, sh
 
     _compare(hip, lambda p: so.edge_geometry(p, None, gcpu, lmax), [pos], [0], 21)
+
+
+# ------------------------------------------------------------------------------------------------- ragged shapes
+# The shapes at which tests/test_gpu_op_edges.py pins the first-order twins, plus those csrc/second.hip itself branches on.
+# Same scheme, same TOL.  Every shape is one the operator accepts; where first order refuses a layout, the refusal is asserted
+# and eqf_*_bwd2 is not launched.
+def _f32(t):
+    return t.float().double()
+
+
+def _randn64(shape, seed, scale=1.0):
+    return _f32(torch.randn(shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * scale)
+
+
+@pytest.mark.parametrize("n", [1, 5, 1023, 1025])
+def test_scaled_silu_bwd2_ragged(n):
+    """one element, and either side of a multiple of the 256-thread block"""
+    from equiformer_amd import ops, so3
+    import fp64_ops as fo
+    x = _randn64((n, 1), 40 + n, 2.0).requires_grad_(True)
+    _compare(lambda t: ops.scaled_silu(t, so3.C_SILU), lambda t: fo.scaled_silu(t, so3.C_SILU), [x], [0], 41)
+
+
+GATES_RAGGED = {  # (S, gated irreps)
+    "tiny": (8, "4x1e+4x2e+4x3e"),                      # Din = 80: far below one 256-thread column block
+    "wide": (384, "192x1e+192x2e+96x3e"),               # Din = 3072 gates included: column blocks with a partial last one
+    "e3_gated_0o": (16, "8x0o+8x1e+4x1o+4x2e"),         # tests/test_gpu_e3.py: the 0o segment is gated, not activated
+}
+
+
+@pytest.mark.parametrize("rows", [1, 5, 9])
+@pytest.mark.parametrize("case", sorted(GATES_RAGGED))
+def test_gate_bwd2_ragged(case, rows):
+    """rows either side of the RB rows a thread of gate_bwd2_kernel walks (4; the first-order kernels: 8)"""
+    from equiformer_amd import ops, so3
+    from equiformer_amd.layout import RowLayout
+    import fp64_ops as fo
+    S, gated = GATES_RAGGED[case]
+    lay = RowLayout(gated)
+    Din = S + sum(m for m, _ in lay.segs) + lay.dim
+    x = _randn64((rows, Din), 42, 1.5).requires_grad_(True)
+    _compare(lambda t: ops.gate(t, S, lay, so3.C_SILU, so3.C_SIGMOID),
+             lambda t: fo.gate(t, S, lay, so3.C_SILU, so3.C_SIGMOID), [x], [0], 43)
+
+
+@pytest.mark.parametrize("rows", [1, 5])
+@pytest.mark.parametrize("G", [1, 3])
+@pytest.mark.parametrize("C", [1, 3, 30, 50, 64])
+def test_lnsilu_bwd2_ragged(C, G, rows):
+    """C < 64 leaves inactive lanes in every wave reduction of lnsilu_bwd2_kernel; C = 1 makes the variance exactly zero (every
+    derivative wrt x and gamma is then exactly zero, on both sides).
+    Inputs: a ramp over the channels of a group (-1.5 .. 1.5) plus 0.4 randn, so that no group is nearly constant.  The second
+    derivative grows like rstd^3, and three plain randn values can lie arbitrarily close together: the first draw of this test
+    (1.3 randn, C = 3, G = 3, 5 rows) held a group of variance 1.1e-3, on which the SAME restatement evaluated in float32 on the
+    CPU is off by 1.2e-5 (1e-7 to 8e-7 on the other shapes) and the kernel by 6.8e-5 -- the conditioning of a three-value
+    LayerNorm in float32, not the lanes this test is about."""
+    from equiformer_amd import ops
+    import fp64_ops as fo
+    g = torch.Generator().manual_seed(44)
+    ramp = torch.linspace(-1.5, 1.5, C, dtype=torch.float64).repeat(G) if C > 1 else torch.zeros(G, dtype=torch.float64)
+    x = _f32(_randn64((rows, C * G), 45, 0.4) + ramp).requires_grad_(True)
+    gamma = _f32(torch.rand(C * G, generator=g, dtype=torch.float64) + 0.5).requires_grad_(True)
+    beta = _f32(torch.randn(C * G, generator=g, dtype=torch.float64)).requires_grad_(True)
+    _compare(lambda t, ga, be: ops.ln_silu(t, ga, be, 1e-5, groups=G), lambda t, ga, be: fo.ln_silu(t, ga, be, 1e-5, groups=G),
+             [x, gamma, beta], [0], 46)
+
+
+def _ln_problem(irr, rows, seed):
+    import fp64_ops as fo
+    import second_order_cases as cases
+    seg = fo.Segs(irr)
+    g = torch.Generator().manual_seed(seed)
+    nw = sum(m for m, _ in seg.segs)
+    nb = sum(m for s, (m, _) in enumerate(seg.segs) if seg.scalar(s))
+    x = _randn64((rows, seg.dim), seed + 1).requires_grad_(True)
+    w = _f32(torch.rand(nw, generator=g, dtype=torch.float64) + 0.5).requires_grad_(True)
+    b = _f32(torch.randn(nb, generator=g, dtype=torch.float64)).requires_grad_(True)
+    return seg, cases.op_layout(irr), x, w, b
+
+
+@pytest.mark.parametrize("rows", [1, 5])
+@pytest.mark.parametrize("irr", ["8x0e+4x1e", "64x0e+32x1e+16x0e", "16x0e+8x0o+8x1e+4x1o+4x2e"])
+def test_layernorm_bwd2_ragged(irr, rows):
+    """segments shorter than a wave, two scalar segments, a 0o segment (the l = -1 branch of make_segtab2: no mean, no bias);
+    1 and 5 rows: a partial workgroup of WPB = 4 waves"""
+    from equiformer_amd import ops
+    import fp64_ops as fo
+    seg, lay, x, w, b = _ln_problem(irr, rows, 47)
+    _compare(lambda t, ww, bb: ops.layer_norm(t, ww, bb, lay, 1e-5), lambda t, ww, bb: fo.layer_norm(t, ww, bb, seg, 1e-5),
+             [x, w, b], [0], 48)
+
+
+def test_layernorm_bwd2_more_affine_weights_than_the_lds_accumulator():
+    """1056 affine weights > GW_S = 1024: layernorm_bwd2_kernel adds straight into g_w (via_lds == false).  First order runs on
+    the layout first; were it to refuse it, that refusal is the result and the second-order kernel is not launched."""
+    from equiformer_amd import lib, ops
+    import fp64_ops as fo
+    seg, lay, x, w, b = _ln_problem("1024x0e+32x1e", 3, 49)
+    dev = _dev()
+    xs, ws, bs = (t.detach().float().to(dev).requires_grad_(True) for t in (x, w, b))
+    try:
+        y = ops.layer_norm(xs, ws, bs, lay, 1e-5)
+        torch.autograd.grad(y.sum(), [xs, ws, bs])
+        torch.cuda.synchronize()
+    except lib.HipLibraryError:
+        with pytest.raises(lib.HipLibraryError):
+            ops.layer_norm(xs, ws, bs, lay, 1e-5)
+        return
+    _compare(lambda t, ww, bb: ops.layer_norm(t, ww, bb, lay, 1e-5), lambda t, ww, bb: fo.layer_norm(t, ww, bb, seg, 1e-5),
+             [x, w, b], [0], 50)
+
+
+@pytest.mark.parametrize("E", [1, 9, 67])
+@pytest.mark.parametrize("H,Kh", [(3, 32), (5, 16), (6, 32), (16, 32), (8, 64), (2, 8)])
+def test_alpha_bwd2_ragged(H, Kh, E):
+    """the (H, Kh) of test_alpha_logits_edges: H Kh no multiple of the 256-thread block, heads of 8 to 64 lanes; E = 1, 9 and 67:
+    below, just above and many times the CH = 8 edges a thread of alpha_bwd2_kernel walks"""
+    from equiformer_amd import ops, so3
+    import fp64_ops as fo
+    a = _randn64((E, H * Kh), 51, 1.5).requires_grad_(True)
+    ad = _randn64((H * Kh,), 52).requires_grad_(True)
+    c = so3.C_SMOOTH_LEAKY_RELU_02
+    _compare(lambda t, d: ops.alpha_logits(t, d, H, Kh, c), lambda t, d: fo.alpha_logits(t, d, H, Kh, c), [a, ad], [0], 53)
+
+
+def _lengths(E, cutoff, seed):
+    """edge lengths over (0.3, cutoff + 0.5), with values within 1e-3 below the cutoff and values beyond it in fixed places
+    (not AT it: the indicator is discontinuous there)"""
+    g = torch.Generator().manual_seed(seed)
+    le = torch.rand(E, generator=g, dtype=torch.float64) * (cutoff + 0.2) + 0.3
+    special = torch.tensor([cutoff - 1e-3, cutoff + 1e-3, cutoff - 3e-4, cutoff + 0.4], dtype=torch.float64)
+    if E > 1:
+        n = min(E - 1, special.numel())
+        le[1:1 + n] = special[:n]
+    return _f32(le).requires_grad_(True)
+
+
+@pytest.mark.parametrize("E", [1, 5, 65])
+def test_rbf_expnorm_bwd2_ragged(E):
+    """one wave per edge, four edges per block"""
+    from equiformer_amd import ops
+    from equiformer_amd.nets.layers import ExpNormalSmearing
+    rbf = ExpNormalSmearing(cutoff_lower=0.0, cutoff_upper=5.0, num_rbf=32, trainable=False)
+    means, betas = rbf.means.double(), rbf.betas.double()
+    dev = _dev()
+    _compare(lambda t: ops.rbf_expnorm(t, means.float().to(dev), betas.float().to(dev), rbf.alpha, 5.0),
+             lambda t: so.rbf_expnorm(t, means, betas, rbf.alpha, 5.0), [_lengths(E, 5.0, 54)], [0], 55)
+
+
+@pytest.mark.parametrize("E", [1, 65])
+@pytest.mark.parametrize("R", [1, 50, 256])
+def test_rbf_gaussian_bwd2_ragged(R, E):
+    """R = 1, 50, 256: one lane, a partial wave, the kernel's limit (R > 256 is refused); E either side of the CH = 64 edges a
+    block of the parameter kernel reduces"""
+    from equiformer_amd import ops
+    g = torch.Generator().manual_seed(56)
+    mean = _f32(torch.rand(1, R, generator=g, dtype=torch.float64)).requires_grad_(True)
+    std = _f32(torch.rand(1, R, generator=g, dtype=torch.float64) * 0.9 + 0.1).requires_grad_(True)
+    weight = _f32(torch.tensor([[1.1]], dtype=torch.float64)).requires_grad_(True)
+    bias = _f32(torch.tensor([[0.05]], dtype=torch.float64)).requires_grad_(True)
+
+    def ref(le, mu, sd, w, b):  # [ref: nets/gaussian_rbf.py:6-40]
+        x = w * (le / 5.0).unsqueeze(-1) + b
+        s = sd.abs() + 1e-5
+        return torch.exp(-0.5 * ((x - mu) / s) ** 2) / ((2 * 3.14159) ** 0.5 * s)
+
+    _compare(lambda le, mu, sd, w, b: ops.rbf_gaussian(le, mu, sd, w, b, 5.0), ref,
+             [_lengths(E, 5.0, 57), mean, std, weight, bias], [0], 58)
+
+
+def test_rbf_gaussian_refuses_more_than_256_basis_functions():
+    """the first-order backward already does (its forward is element-wise and has no limit), with or without create_graph:
+    nothing reaches eqf_rbf_gaussian_bwd2 with R > 256"""
+    from equiformer_amd import lib, ops
+    dev = _dev()
+    z = lambda *s: torch.rand(*s, device=dev) + 0.1  # noqa: E731
+    for create_graph in (False, True):
+        le = z(3).requires_grad_(True)
+        out = ops.rbf_gaussian(le, z(1, 257), z(1, 257), z(1, 1), z(1, 1), 5.0)
+        with pytest.raises(lib.HipLibraryError):
+            torch.autograd.grad(out.sum(), le, create_graph=create_graph)
+
+
+@pytest.mark.parametrize("E", [1, 65])
+def test_rbf_bessel_bwd2_ragged(E):
+    """E either side of the EPB = 64 edges of a block"""
+    from equiformer_amd import ops
+    from oracle import nets as onets
+    ref = onets.RadialBasis(16, cutoff=5.0, rbf={"name": "spherical_bessel"}).double()
+    freq = _f32(ref.rbf.frequencies.detach().double() * (1.0 + 0.01 * _randn64((16,), 59))).requires_grad_(True)
+
+    def fref(le, fr):
+        x = le / 5.0
+        env = 1 + ref.a * x ** 5 + ref.b * x ** 6 + ref.c * x ** 7
+        env = torch.where(x < 1, env, torch.zeros_like(x))
+        return env[:, None] * (ref.rbf.norm_const / x[:, None] * torch.sin(fr * x[:, None]))
+
+    _compare(lambda le, fr: ops.rbf_bessel(le, fr, 5.0), fref, [_lengths(E, 5.0, 60), freq], [0], 61)
+
+
+@pytest.mark.parametrize("which", ["one_edge", "ragged"])
+@pytest.mark.parametrize("lmax", [1, 2, 3])
+def test_edge_geometry_bwd2_ragged(lmax, which):
+    """a graph of one edge, and a ragged one: the in-degrees of fo.SEG_LENGTHS (0 .. 130), sources among the first seven nodes,
+    so that three nodes are nobody's source and get an exactly zero source sum.  fo.ragged_graph itself draws self-loops
+    (four with this seed): edges of length zero, where the spherical harmonics have no derivative -- a source equal to its
+    destination is moved to the next of the seven."""
+    from types import SimpleNamespace
+    from equiformer_amd import ops
+    from equiformer_amd.graph import EdgeGraph
+    import fp64_ops as fo
+    dev = _dev()
+    if which == "one_edge":
+        graph, _ = EdgeGraph.from_edges(torch.tensor([2]).to(dev), torch.tensor([0]).to(dev), 3)
+    else:
+        g = torch.Generator().manual_seed(62)
+        dst = torch.repeat_interleave(torch.arange(len(fo.SEG_LENGTHS)), torch.tensor(fo.SEG_LENGTHS))
+        src = torch.randint(0, 7, (dst.numel(),), generator=g)
+        src = torch.where(src == dst, (src + 1) % 7, src)
+        shuffle = torch.randperm(dst.numel(), generator=g)
+        graph, _ = EdgeGraph.from_edges(src[shuffle].to(dev), dst[shuffle].to(dev), len(fo.SEG_LENGTHS))
+        assert int((graph.src == graph.dst).sum()) == 0
+    gcpu = SimpleNamespace(src=graph.src.cpu(), dst=graph.dst.cpu())
+    pos = _randn64((graph.N, 3), 63, 2.0).requires_grad_(True)
+
+    def hip(p):
+        _, length, sh = ops.edge_geometry(p, None, graph, lmax)
+        return length, sh
+
+    _compare(hip, lambda p: so.edge_geometry(p, None, gcpu, lmax), [pos], [0], 64)

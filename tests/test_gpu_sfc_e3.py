@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fp64_ops  # noqa: E402
+from fp64_tp import blocks as _blocks, reference  # noqa: E402  (the restatement of the operator from its path table)
 from equiformer_amd import ops, so3  # noqa: E402
 from equiformer_amd.layout import DtpTable, RowLayout  # noqa: E402
 
@@ -47,37 +48,6 @@ def _dev():
 
 def _rel(a, b):
     return ((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30)).item()
-
-
-def _blocks(spec, weight):
-    return [weight[o:o + K * N].view(K, N) for (_, K, N, _), o in zip(spec.degs, spec.w_offs)]
-
-
-def reference(spec, x, M, w, blocks, weight2, bias, bias2):
-    """fp64, differentiable.  blocks: one [K, N1] matrix per consumer segment, in spec.degs order."""
-    table, lay = spec.table, spec.out_layout
-    E = x.shape[0]
-    mid = {}
-    for p in table.paths:
-        d1, d3, mul = 2 * p["l1"] + 1, 2 * p["l3"] + 1, p["mul"]
-        xs = x[:, p["in_off"]:p["in_off"] + d1 * mul].view(E, d1, mul)
-        Mp = M[:, p["m_off"]:p["m_off"] + d1 * d3].view(E, d1, d3)
-        t = torch.einsum("eik,eiu->eku", Mp, xs)
-        if w is not None:
-            t = t * w[:, None, p["w_off"]:p["w_off"] + mul]
-        mid.setdefault((p["l3"], p["p3"]), []).append((p["out_ch"], t))
-    outs, out2 = [], None
-    for (l3, K, N1, _), par, W in zip(spec.degs, spec.pars, blocks):
-        m = torch.cat([t for _, t in sorted(mid[(l3, par)], key=lambda q: q[0])], dim=2)  # [E, d3, K]
-        assert m.shape[2] == K
-        o = m @ W
-        if (l3, par) == (0, 1):
-            if bias is not None:
-                o = o + bias
-            if spec.n2:
-                out2 = m[:, 0] @ weight2.view(K, spec.n2) + bias2
-        outs.append(o.reshape(E, -1))
-    return torch.cat(outs, dim=1), out2
 
 
 class Case:
