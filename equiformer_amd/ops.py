@@ -3174,3 +3174,112 @@ class _DpLogitsBwd(Function):
 
 def dp_logits(q, k, graph, H, layout):
     return _DpLogits.apply(q, k, graph, H, layout)
+
+
+# ------------------------------------------------------------------------- the IS2RE + IS2RS step around the OC20 model
+def _tags_arg(tags, rows, what):
+    """([N] int32 / int64 device tags as they are, is64): the kernels read either width, no conversion launch"""
+    if not tags.is_cuda:
+        raise HipOnlyError("the Equiformer hot path runs on MI355X only (got a %s tensor); there is no CPU fallback" % tags.device)
+    if tags.dtype not in (torch.int32, torch.int64):
+        raise HipOnlyError("tags are int32 / int64, got %s" % tags.dtype)
+    if tags.numel() != rows:
+        raise ValueError("%s: tags has %d entries, the batch has %d rows" % (what, tags.numel(), rows))
+    return _c(tags), int(tags.dtype == torch.int64)
+
+
+def is2rs_perturb(pos, pos_relaxed, tags, batch, p_perturb=0.5, f_min=0.0, noise_std=0.3, seed=0):
+    """(pos_out, factor, noise_vec, selected) of the IS2RS perturbation, one launch, no gradient
+    [ref: oc20/trainer/base_trainer_v2.py:81-126]: pos, pos_relaxed [N, 3] fp32, tags [N] int32 / int64, batch [N] int32;
+    `selected` (the structure's draw, per atom) comes back as bool.  The atoms with selected and tags > 0 move to
+    pos * factor + (1 - factor) * pos_relaxed + noise_vec (separately rounded fp32 operations), every other row keeps its
+    bits.  Every random number is a function of (seed, index) alone: the same seed gives the same bits."""
+    pos, pos_relaxed, batch = _c(pos.detach()), _c(pos_relaxed.detach()), _c(batch)
+    _chk(pos, pos_relaxed, batch)
+    if batch.dtype != torch.int32:
+        raise HipOnlyError("kernels take int32 indices, got %s" % batch.dtype)
+    N = pos.shape[0]
+    if tuple(pos.shape) != (N, 3) or tuple(pos_relaxed.shape) != (N, 3) or batch.numel() != N:
+        raise ValueError("is2rs_perturb: pos %s, pos_relaxed %s, batch %s" % (
+            tuple(pos.shape), tuple(pos_relaxed.shape), tuple(batch.shape)))
+    if not 0.0 <= float(f_min) <= 1.0 or not float(noise_std) >= 0.0:
+        raise ValueError("is2rs_perturb: f_min %r outside [0, 1] or noise_std %r negative" % (f_min, noise_std))
+    tags, is64 = _tags_arg(tags, N, "is2rs_perturb")
+    pos_out, noise_vec = torch.empty_like(pos), torch.empty_like(pos)
+    factor = torch.empty(N, dtype=torch.float32, device=pos.device)
+    selected = torch.empty(N, dtype=torch.bool, device=pos.device)
+    call("eqf_is2rs_perturb", _p(pos), _p(pos_relaxed), ctypes.c_void_p(_nonnull(tags)), is64, _p(batch), N, float(p_perturb),
+         float(f_min), float(noise_std), int(seed) & (2 ** 64 - 1), _p(pos_out), _p(factor), _p(noise_vec),
+         ctypes.c_void_p(selected.data_ptr()), _stream())
+    return pos_out, factor, noise_vec, selected
+
+
+class _Is2rsLoss(Function):
+    """First order only."""
+
+    @staticmethod
+    def forward(ctx, pred_y, pred_pos, y, pos, pos_relaxed, tags, is64, row_mask, weights, stats, norm, threshold):
+        pred_y, pred_pos = _c(pred_y), _c(pred_pos)
+        loss = torch.empty((), device=pred_y.device, dtype=torch.float32)
+        ctx.consts = (pred_pos.shape[0], pred_y.numel(), is64, tuple(float(v) for v in norm))
+        N, nB, is64, norm = ctx.consts
+        call("eqf_is2rs_loss_fwd", _p(pred_y), _p(y), _p(pred_pos), _p(pos), _p(pos_relaxed), ctypes.c_void_p(_nonnull(tags)),
+             is64, _p(row_mask), _p(weights), N, nB, *norm, float(threshold), _p(loss), _p(stats), _stream())
+        ctx.save_for_backward(pred_y, pred_pos, y, pos, pos_relaxed, tags, row_mask, weights, stats)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        pred_y, pred_pos, y, pos, pos_relaxed, tags, row_mask, weights, stats = ctx.saved_tensors
+        N, nB, is64, norm = ctx.consts
+        d_loss = d_loss.to(torch.float32)
+        d_pred_y, d_pred_pos = torch.empty_like(pred_y), torch.empty_like(pred_pos)
+        call("eqf_is2rs_loss_bwd", _p(d_loss), _p(pred_y), _p(y), _p(pred_pos), _p(pos), _p(pos_relaxed),
+             ctypes.c_void_p(_nonnull(tags)), is64, _p(row_mask), _p(weights), _p(stats), N, nB, *norm, _p(d_pred_y),
+             _p(d_pred_pos), _stream())
+        return d_pred_y, d_pred_pos, None, None, None, None, None, None, None, None, None, None
+
+
+def is2rs_loss(pred_y, pred_pos, y, pos, pos_relaxed, tags, weights, target_mean, target_std, positions_mean, positions_std,
+               threshold=0.02, row_mask=None, stats_out=None):
+    """loss (0-dim) = w[0] mean|pred_y - (y - mean) / std| + w[1] mean over the free rows (tags > 0) and their 3 components of
+    |pred_pos - ((pos_relaxed - pos) - positions_mean) / positions_std| [ref: oc20/trainer/energy_trainer_v2.py:413-442 with the
+    `mae` losses]; one launch forward, one backward, nothing read back.  pos: the (perturbed) positions the model saw.  tags:
+    [N] int32 / int64.  weights: [2] fp32 DEVICE tensor {energy, auxiliary}; positions_mean / positions_std: a number or three
+    (per component); row_mask: [N] fp32, 1 real / 0 phantom (the node_mask of a padded batch), None = all real.  stats_out: the
+    caller's 8-float device buffer {loss_e, loss_aux, n_free, energy_mae, energy_mse, energy_within_threshold, pos_mae, 0}
+    (:445-459) -- the same address in every captured bucket; the backward reads n_free from it, so a buffer shared between calls
+    is backpropagated before the next forward (None: a fresh one per call).  An empty free set contributes an exact 0."""
+    y = _c(y.detach().to(torch.float32).reshape(-1))
+    pos, pos_relaxed = _c(pos.detach()), _c(pos_relaxed.detach())
+    pred_pos = _c(pred_pos)  # (the attention head hands out a column slice)
+    _chk(pred_y, pred_pos, y, pos, pos_relaxed, row_mask, weights, stats_out)
+    N, nB = pred_pos.shape[0], pred_y.numel()
+    if nB < 1 or y.numel() != nB or tuple(pred_pos.shape) != (N, 3) or tuple(pos.shape) != (N, 3) or tuple(pos_relaxed.shape) != (N, 3):
+        raise ValueError("is2rs_loss: pred_y %s, y %s, pred_pos %s, pos %s, pos_relaxed %s" % (
+            tuple(pred_y.shape), tuple(y.shape), tuple(pred_pos.shape), tuple(pos.shape), tuple(pos_relaxed.shape)))
+    tags, is64 = _tags_arg(tags, N, "is2rs_loss")
+    if row_mask is not None and row_mask.numel() != N:
+        raise ValueError("row_mask has %d entries, the batch has %d rows" % (row_mask.numel(), N))
+    if weights.numel() != 2 or weights.dtype != torch.float32:
+        raise ValueError("weights: 2 fp32 device words {energy, auxiliary}")
+    if stats_out is None:
+        stats_out = torch.empty(8, device=pred_y.device, dtype=torch.float32)
+    elif stats_out.numel() != 8 or stats_out.dtype != torch.float32:
+        raise ValueError("stats_out: an 8-float device buffer")
+    p_mean, p_std = _three(positions_mean), _three(positions_std)
+    if float(target_std) == 0.0 or 0.0 in p_std:
+        raise ValueError("is2rs_loss: target_std and positions_std must not be zero")
+    norm = (float(target_mean), float(target_std)) + p_mean + p_std
+    return _Is2rsLoss.apply(pred_y, pred_pos, y, pos, pos_relaxed, tags, is64, row_mask, weights, stats_out, norm, threshold)
+
+
+def _three(v):
+    """a number, or a sequence of three (per component), as three floats"""
+    if isinstance(v, (int, float)):
+        return (float(v),) * 3
+    v = tuple(float(x) for x in v)
+    if len(v) != 3:
+        raise ValueError("expected one value or three (per component), got %d" % len(v))
+    return v

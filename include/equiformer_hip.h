@@ -701,6 +701,58 @@ int eqf_dens_loss_bwd(const float* d_loss, const float* pred_y, const float* y, 
                       const float* stats, int N, int nB, double task_mean, double task_std, double noise_std,
                       float* d_pred_y, float* d_pred_dy, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The IS2RE + IS2RS training step around the OC20 model: perturbation of a batch, loss + metrics
+ * ------------------------------------------------------------------------------------------- */
+
+/* Interpolation between the initial and the relaxed positions plus Gaussian noise (Noisy Nodes), one launch.
+ * [ref: oc20/trainer/base_trainer_v2.py:81-126 interpolate_init_relaxed_pos]
+ *   selected[i]    = u_struct(batch[i]) < p_perturb          one uniform draw per STRUCTURE, the same for all its atoms
+ *   factor[i]      = f_min + (1 - f_min) u_atom(i)            every row; f_min <= factor < 1
+ *   noise_vec[i,c] = noise_std * n(3 i + c)                   every row, moved or not
+ *   pos_out[i]     = selected[i] && tags[i] > 0 ? (pos[i] factor[i] + (1 - factor[i]) pos_relaxed[i]) + noise_vec[i]
+ *                                               : pos[i]      (the bits of pos)
+ * The moved position is formed from separately rounded fp32 operations in the order written (two products, 1 - factor,
+ * two sums), so the stored factor and noise_vec reproduce it bit for bit.  The reference's uniform-direction noise
+ * (:98-106) is overwritten by its :108 and is not drawn.  Draws as eqf_dens_corrupt (counter-based: a function of seed, a
+ * stream tag of this launch's own and the index -- the structure id, the row, 3 row + c).  tags: [N] int32, or int64 when
+ * tags_is64 != 0 (the dtype a loader carries; no conversion launch).  selected is one byte per row, 0 or 1.  pos_out may
+ * alias pos.  `seed` is by value: this launch moves atoms, so it precedes the radius graph of the step and stays outside
+ * a HIP-graph capture. */
+int eqf_is2rs_perturb(const float* pos, const float* pos_relaxed, const void* tags, int tags_is64, const int* batch, int N,
+                      float p_perturb, float f_min, float noise_std, unsigned long long seed, float* pos_out,
+                      float* factor, float* noise_vec, unsigned char* selected, void* stream);
+
+/* The two-term loss (`mae` / `mae`, what every shipped _aux configuration uses) and the step's metrics, one launch.
+ * [ref: oc20/trainer/energy_trainer_v2.py:413-442 _compute_loss, :445-459 _compute_metrics]
+ *   loss_e   = mean_b |pred_y[b] - (y[b] - e_mean) / e_std|                                   b < nB
+ *   loss_aux = mean over the free real rows (tags > 0, n_free of them) and their 3 components of
+ *              |pred_pos[i,c] - ((pos_relaxed[i,c] - pos[i,c]) - p_mean_c) / p_std_c|          pos: the PERTURBED positions
+ *   loss[0]  = weights[0] loss_e + weights[1] loss_aux
+ *   stats[8] = {loss_e, loss_aux, n_free, energy_mae, energy_mse, energy_within_threshold, pos_mae, 0}: with
+ *   e = pred_y e_std + e_mean - y the mean of |e|, of e^2 and the share of the nB structures with |e| < threshold;
+ *   pos_mae = mean over the same rows and components of |pred_pos p_std_c + p_mean_c - (pos_relaxed - pos)| (Angstrom).
+ * An empty free set contributes exactly 0 and loss_aux / pos_mae are 0 (the reference gets NaN from the empty mean).
+ * row_mask [N] (1 real, 0 phantom: the node_mask of a padded batch) may be NULL = all rows real; phantom rows are never
+ * read.  `weights` [2] is DEVICE memory: a launch captured in a HIP graph sees the auxiliary weight the host decayed
+ * between two replays (:462-470).  tags as eqf_is2rs_perturb.  One workgroup, fp64 arithmetic from the fp32 inputs,
+ * fixed-order reduction: no atomics, no workspace, two calls give the same bits.  nB < 1 and a zero e_std / p_std_c are
+ * argument errors, N == 0 is legal. */
+int eqf_is2rs_loss_fwd(const float* pred_y, const float* y, const float* pred_pos, const float* pos,
+                       const float* pos_relaxed, const void* tags, int tags_is64, const float* row_mask,
+                       const float* weights, int N, int nB, double e_mean, double e_std, double p_mean_x, double p_mean_y,
+                       double p_mean_z, double p_std_x, double p_std_y, double p_std_z, double threshold, float* loss,
+                       float* stats, void* stream);
+/* d_pred_y[nB] = g weights[0] / nB sign(e), d_pred_pos[N,3] = g weights[1] / (3 n_free) sign(d) on the free real rows (n_free:
+ * stats[2] of the forward); exactly 0 where the difference vanishes (the subgradient torch takes), on fixed atoms and on
+ * phantom rows.  g = d_loss[0], read on the device.  First order only.
+ * [ref: the `loss.backward()` of oc20/trainer/energy_trainer_v2.py:413-442] */
+int eqf_is2rs_loss_bwd(const float* d_loss, const float* pred_y, const float* y, const float* pred_pos, const float* pos,
+                       const float* pos_relaxed, const void* tags, int tags_is64, const float* row_mask,
+                       const float* weights, const float* stats, int N, int nB, double e_mean, double e_std,
+                       double p_mean_x, double p_mean_y, double p_mean_z, double p_std_x, double p_std_y, double p_std_z,
+                       float* d_pred_y, float* d_pred_pos, void* stream);
+
 /* Running evaluation metrics, one launch per batch.  [ref: engine.py:136-139 evaluate (L1 loss and MAE meters),
  * main_md17.py:451-462 evaluate (energy / force loss and MAE meters), the OC20 trainer's _compute_metrics
  * (energy_trainer_v2.py:445-459: energy_mae, energy_mse, energy_within_threshold) -- each a `.item()` read-back per batch]
