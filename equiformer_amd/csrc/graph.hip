@@ -407,20 +407,23 @@ __global__ __launch_bounds__(256) void edge_geom_bwd_kernel(const float* __restr
 
 // ---------------------------------------------------------------------------------------------- radial basis
 constexpr float kGaussA = 2.5066272160016134f;  // sqrt(2 * 3.14159), the reference's truncated pi
+// x - mean is formed in double and rounded once: (x - mean) / std with std = 0.05 turns ONE float ulp of x into 3e-4 of a
+// d_len whose terms cancel, and x = weight * len * (1 / cutoff) + bias in float is up to two ulps off (the rounded
+// reciprocal alone cost an ulp).  Three double operations per basis function; everything after the difference is float.
 
 __global__ __launch_bounds__(256) void rbf_gauss_fwd_kernel(const float* __restrict__ len, long total, int R,
                                                             const float* __restrict__ mean,
                                                             const float* __restrict__ stdp,
                                                             const float* __restrict__ weight,
-                                                            const float* __restrict__ bias, float inv_cut,
+                                                            const float* __restrict__ bias, double inv_cut,
                                                             float* __restrict__ out) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const long e = idx / R;
   const int r = (int)(idx - e * R);
-  const float x = weight[0] * (len[e] * inv_cut) + bias[0];
+  const double x = (double)weight[0] * ((double)len[e] * inv_cut) + (double)bias[0];
   const float sd = fabsf(stdp[r]) + 1e-5f;
-  const float t = (x - mean[r]) / sd;
+  const float t = (float)(x - (double)mean[r]) / sd;
   out[idx] = __expf(-0.5f * t * t) / (kGaussA * sd);
 }
 
@@ -429,7 +432,7 @@ __global__ __launch_bounds__(256) void rbf_gauss_bwd_kernel(const float* __restr
                                                             int E, int R, const float* __restrict__ mean,
                                                             const float* __restrict__ stdp,
                                                             const float* __restrict__ weight,
-                                                            const float* __restrict__ bias, float inv_cut,
+                                                            const float* __restrict__ bias, double inv_cut,
                                                             float* __restrict__ d_mean, float* __restrict__ d_std,
                                                             float* __restrict__ d_weight, float* __restrict__ d_bias,
                                                             int CH) {
@@ -437,11 +440,13 @@ __global__ __launch_bounds__(256) void rbf_gauss_bwd_kernel(const float* __restr
   const int e0 = blockIdx.x * CH, e1 = min(E, e0 + CH);
   float am = 0.f, as = 0.f, aw = 0.f, ab = 0.f;
   if (r < R) {
-    const float w = weight[0], b = bias[0], mu = mean[r], sp = stdp[r];
+    const float sp = stdp[r];
+    const double w = weight[0], bmu = (double)bias[0] - (double)mean[r];
     const float sd = fabsf(sp) + 1e-5f, sgn = (sp >= 0.f) ? 1.f : -1.f;
     for (int e = e0; e < e1; ++e) {
-      const float xs = len[e] * inv_cut;
-      const float t = (w * xs + b - mu) / sd;
+      const double xd = (double)len[e] * inv_cut;
+      const float xs = (float)xd;
+      const float t = (float)(w * xd + bmu) / sd;
       const float o = __expf(-0.5f * t * t) / (kGaussA * sd);
       const float go = g[(long)e * R + r] * o;
       const float dxv = -go * t / sd;
@@ -470,20 +475,21 @@ __global__ __launch_bounds__(256) void rbf_gauss_dlen_kernel(const float* __rest
                                                              int E, int R, const float* __restrict__ mean,
                                                              const float* __restrict__ stdp,
                                                              const float* __restrict__ weight,
-                                                             const float* __restrict__ bias, float inv_cut,
+                                                             const float* __restrict__ bias, double inv_cut,
                                                              float* __restrict__ d_len) {
   const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (e >= E) return;
-  const float w = weight[0], x = w * (len[e] * inv_cut) + bias[0];
+  const float w = weight[0];
+  const double x = (double)w * ((double)len[e] * inv_cut) + (double)bias[0];
   float acc = 0.f;
   for (int r = lane; r < R; r += 64) {
     const float sd = fabsf(stdp[r]) + 1e-5f;
-    const float t = (x - mean[r]) / sd;
+    const float t = (float)(x - (double)mean[r]) / sd;
     const float o = __expf(-0.5f * t * t) / (kGaussA * sd);
     acc += g[(long)e * R + r] * (-o * t / sd);
   }
   acc = wave_sum(acc);
-  if (lane == 0) d_len[e] = acc * w * inv_cut;
+  if (lane == 0) d_len[e] = acc * (w * (float)inv_cut);
 }
 
 __global__ __launch_bounds__(256) void rbf_expnorm_fwd_kernel(const float* __restrict__ len, long total, int R,
@@ -533,10 +539,12 @@ struct BesselEnv {
 __device__ __forceinline__ BesselEnv bessel_env(float x) {
   BesselEnv r{0.f, 0.f, 0.f};
   if (x < 1.f) {
-    const float x2 = x * x, x3 = x2 * x, x4 = x2 * x2, x5 = x4 * x;
-    r.e0 = 1.f + x5 * (-21.f + x * (35.f - 15.f * x));
-    r.e1 = x4 * (-105.f + x * (210.f - 105.f * x));
-    r.e2 = x3 * (-420.f + x * (1050.f - 630.f * x));
+    // 1 - 21 x^5 + 35 x^6 - 15 x^7 has a triple root at x = 1: in its expanded form the terms cancel there (1e-3 of the
+    // envelope is rounding at x = 0.97); factored, every term is positive and u = 1 - x is exact from x = 0.5 on
+    const float u = 1.f - x, x2 = x * x, x3 = x2 * x, x4 = x2 * x2;
+    r.e0 = u * u * u * (1.f + x * (3.f + x * (6.f + x * (10.f + 15.f * x))));
+    r.e1 = -105.f * x4 * (u * u);
+    r.e2 = -210.f * x3 * (u * (2.f - 3.f * x));
   }
   return r;
 }
@@ -743,7 +751,7 @@ int eqf_rbf_gaussian_fwd(const float* len, int E, int R, const float* mean, cons
   if (E <= 0) return 0;
   const long total = (long)E * R;
   hipLaunchKernelGGL(rbf_gauss_fwd_kernel, dim3(eqf_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, len, total, R,
-                     mean, std, weight, bias, 1.f / cutoff, out);
+                     mean, std, weight, bias, 1.0 / (double)cutoff, out);
   EQF_CHECK_LAUNCH();
   return 0;
 }
@@ -758,11 +766,11 @@ int eqf_rbf_gaussian_bwd(const float* len, const float* d_out, int E, int R, con
   const int CH = 64;
   const int threads = ((R + 63) / 64) * 64;
   hipLaunchKernelGGL(rbf_gauss_bwd_kernel, dim3(eqf_cdiv(E, CH)), dim3(threads), 0, (hipStream_t)stream, len, d_out, E,
-                     R, mean, std, weight, bias, 1.f / cutoff, d_mean, d_std, d_weight, d_bias, CH);
+                     R, mean, std, weight, bias, 1.0 / (double)cutoff, d_mean, d_std, d_weight, d_bias, CH);
   EQF_CHECK_LAUNCH();
   if (d_len) {
     hipLaunchKernelGGL(rbf_gauss_dlen_kernel, dim3(eqf_cdiv(E, 4)), dim3(256), 0, (hipStream_t)stream, len, d_out, E, R,
-                       mean, std, weight, bias, 1.f / cutoff, d_len);
+                       mean, std, weight, bias, 1.0 / (double)cutoff, d_len);
     EQF_CHECK_LAUNCH();
   }
   return 0;
