@@ -715,11 +715,6 @@ int eqf_gemm_nt(const float* A, eqf_rows ra, const float* B, int ldb, float* C, 
   return launch_rows<A_MEM, B_NK>(a, (hipStream_t)stream);
 }
 
-int eqf_gemm_tn(const float* A, eqf_rows ra, const float* B, eqf_rows rb, float* C, int ldc, int M, int N, int R,
-                void* stream) {
-  return eqf_gemm_tn_colsum(A, ra, B, rb, C, ldc, M, N, R, nullptr, nullptr, stream);
-}
-
 int eqf_gemm_tn_colsum(const float* A, eqf_rows ra, const float* B, eqf_rows rb, float* C, int ldc, int M, int N, int R,
                        float* colsum_a, float* colsum_b, void* stream) {
   if (!A || !B || !C || ra.d < 1 || rb.d < 1) return EQF_E_BADARG;

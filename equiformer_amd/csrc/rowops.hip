@@ -841,11 +841,6 @@ int eqf_lnsilu_fwd(const float* x, const float* gamma, const float* beta, float*
   return eqf_lnsilu_group_fwd(x, gamma, beta, y, rows, C, 1, eps, stream);
 }
 
-int eqf_lnsilu_bwd(const float* x, const float* gamma, const float* beta, const float* dy, float* dx, float* d_gamma,
-                   float* d_beta, int rows, int C, float eps, void* stream) {
-  return eqf_lnsilu_group_bwd(x, gamma, beta, dy, dx, d_gamma, d_beta, rows, C, 1, eps, stream);
-}
-
 int eqf_lnsilu_group_bwd(const float* x, const float* gamma, const float* beta, const float* dy, float* dx,
                          float* d_gamma, float* d_beta, int rows, int C, int groups, float eps, void* stream) {
   if (!x || !gamma || !beta || !dy || !dx || !d_gamma || !d_beta || C < 1 || groups < 1 || groups > 65535)

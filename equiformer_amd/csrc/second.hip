@@ -640,11 +640,6 @@ int eqf_lnsilu_group_bwd2(const float* x, const float* gamma, const float* beta,
   return 0;
 }
 
-int eqf_lnsilu_bwd2(const float* x, const float* gamma, const float* beta, const float* dy, const float* c, float* g_x,
-                    float* g_gamma, float* g_beta, float* g_dy, int rows, int C, float eps, void* stream) {
-  return eqf_lnsilu_group_bwd2(x, gamma, beta, dy, c, g_x, g_gamma, g_beta, g_dy, rows, C, 1, eps, stream);
-}
-
 int eqf_layernorm_bwd2(const float* x, const float* weight, const float* dy, const float* c, float* g_x, float* g_weight,
                        float* g_dy, int rows, const eqf_irreps* irreps, float eps, void* stream) {
   if (!x || !weight || !dy || !c || !g_x || !g_weight || !g_dy || !irreps || irreps->nseg < 1 ||

@@ -93,7 +93,6 @@ SIGNATURES = {
     "eqf_rbf_bessel_bwd": [c_fp, c_fp, c_int, c_int, c_fp, _f, c_fp, c_fp, c_fp],
     "eqf_gemm_nn": [c_fp, EqfRows, c_fp, c_int, c_fp, EqfRows, c_fp, c_int, c_int, c_int, c_int, c_fp],
     "eqf_gemm_nt": [c_fp, EqfRows, c_fp, c_int, c_fp, EqfRows, c_fp, c_int, c_int, c_int, c_int, c_fp],
-    "eqf_gemm_tn": [c_fp, EqfRows, c_fp, EqfRows, c_fp, c_int, c_int, c_int, c_int, c_fp],
     "eqf_gemm_tn_colsum": [c_fp, EqfRows, c_fp, EqfRows, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp],
     "eqf_gemm_group": [ctypes.POINTER(EqfGemmDesc), c_int, c_fp],
     "eqf_gemmx_group": [ctypes.POINTER(EqfGemmDesc), c_int, c_int, c_fp],
@@ -132,7 +131,6 @@ SIGNATURES = {
     "eqf_silu_fwd": [c_fp, c_fp, _long, _f, c_fp],
     "eqf_silu_bwd": [c_fp, c_fp, c_fp, _long, _f, c_fp],
     "eqf_lnsilu_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, _f, c_fp],
-    "eqf_lnsilu_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, _f, c_fp],
     "eqf_lnsilu_group_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, _f, c_fp],
     "eqf_lnsilu_group_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, _f, c_fp],
     "eqf_fold_weight_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp],
@@ -163,7 +161,6 @@ SIGNATURES = {
     "eqf_attn_aggregate_bwd_dseed": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, _P_IRR, _f, _u64, c_fp, c_fp],
     "eqf_silu_bwd2": [c_fp, c_fp, c_fp, c_fp, c_fp, _long, _f, c_fp],
     "eqf_gate_bwd2": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, _P_IRR, _f, _f, c_fp],
-    "eqf_lnsilu_bwd2": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, _f, c_fp],
     "eqf_lnsilu_group_bwd2": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, _f, c_fp],
     "eqf_layernorm_bwd2": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, _P_IRR, _f, c_fp],
     "eqf_alpha_bwd2": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, _f, c_fp],

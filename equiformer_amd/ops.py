@@ -268,14 +268,20 @@ class _LayerNorm(Function):
                 None, None
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
-        dw, db = _zeros2(weight.numel(), ctx.nb, x.device)
-        defer = _can_defer(weight, bias)  # the affine gradients wait for the end of the pass (_defer_norm_wgrad)
-        call("eqf_layernorm_bwd", _p(x), _p(weight), _p(dy), _p(rstd), _p(mean0), _p(dx), None if defer else _p(dw),
-             None if defer else _p(db), x.shape[0], ctx.layout.c_ref, _stream())
-        if defer:
-            _defer_norm_wgrad(weight, bias, x, dy, rstd, mean0, ctx.layout, dw, db)
-        return dx, dw, db, None, None
+        return _ln_bwd(x, weight, dy, rstd, mean0, ctx.layout, ctx.nb, want=True, bias=bias) + (None, None)
+
+
+def _ln_bwd(x, weight, dy, rstd, mean0, layout, nb, want, bias=None):
+    """(dx, d_weight, d_bias): first order, eqf_layernorm_bwd.  bias: the bias parameter, handed over by a plain backward
+    pass -- where weight and bias allow it the affine gradients wait for the end of that pass (_defer_norm_wgrad)."""
+    dx = torch.empty_like(x)
+    dw, db = _zeros2(weight.numel(), nb, x.device) if want else (None, None)
+    defer = bias is not None and _can_defer(weight, bias)
+    call("eqf_layernorm_bwd", _p(x), _p(weight), _p(dy), _p(rstd), _p(mean0), _p(dx), None if defer else _p(dw),
+         None if defer else _p(db), x.shape[0], layout.c_ref, _stream())
+    if defer:
+        _defer_norm_wgrad(weight, bias, x, dy, rstd, mean0, layout, dw, db)
+    return dx, dw, db
 
 
 class _LayerNormBwd(Function):
@@ -286,16 +292,12 @@ class _LayerNormBwd(Function):
     def forward(ctx, x, weight, dy, rstd, mean0, layout, eps, nb):
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
         want = _want_param_grads()
-        dw, db = _zeros2(weight.numel(), nb, x.device) if want else (None, None)
-        call("eqf_layernorm_bwd", _p(x), _p(weight), _p(dy), _p(rstd), _p(mean0), _p(dx), _p(dw), _p(db), x.shape[0],
-             layout.c_ref, _stream())
+        dx, dw, db = _ln_bwd(x, weight, dy, rstd, mean0, layout, nb, want)
         ctx.save_for_backward(x, weight, dy)
         ctx.layout, ctx.eps = layout, eps
-        if not want:
-            return dx, None, None
-        ctx.mark_non_differentiable(dw, db)
+        if want:
+            ctx.mark_non_differentiable(dw, db)
         return dx, dw, db
 
     @staticmethod
@@ -524,15 +526,10 @@ class LinearSpec:
         return self.bias_out_off, self.bias_dim
 
 
-# per-degree / dense linears on the bf16 matrix cores (csrc/gemmx.hip) in every matrix mode but "fp32"; the switch exists for
-# A/B measurements (tools/) and cross-checks
-_gemmx = [True]
-
-
 def _gemm_group(descs, st):
     """One launch per kind for up to 8 GEMMs: eqf_gemmx_group (split-precision / bf16 planes on the bf16 matrix cores) in the
     matrix modes split / bf16 / split6, eqf_gemm_group (exact-fp32 MFMA) in the mode fp32."""
-    m = _MATRIX_MODES[_matrix_mode[0]] if _gemmx[0] else None
+    m = _MATRIX_MODES[_matrix_mode[0]]
     step = 8 if m is None else 24
     for i in range(0, len(descs), step):
         chunk = descs[i:i + step]
@@ -562,12 +559,6 @@ def _lin_fwd_descs(x, weight, bias, spec):
     return out, descs
 
 
-def _lin_fwd(x, weight, bias, spec):
-    out, descs = _lin_fwd_descs(x, weight, bias, spec)
-    _gemm_group(descs, _stream())
-    return out
-
-
 def _lin_dgrad_descs(dy, weight, spec):
     n = dy.shape[0]
     Din, Dout = spec.in_layout.dim, spec.out_layout.dim
@@ -578,12 +569,6 @@ def _lin_dgrad_descs(dy, weight, spec):
         descs.append(_desc(1, (dy, out_off), rows(d, Dout, N), (weight, w_off), N, (dx, in_off), rows(d, Din, K), None,
                            n * d, K, N))
     return dx, descs
-
-
-def _lin_dgrad(dy, weight, spec):
-    dx, descs = _lin_dgrad_descs(dy, weight, spec)
-    _gemm_group(descs, _stream())
-    return dx
 
 
 def _lin_wgrad_descs(x, dy, spec, dw, db=None):
@@ -674,20 +659,7 @@ def _launch_queue(q, early=False):
         entries = ready
     descs = []
     for (w, b, x, dy, spec, fused_b, aw, ab) in entries:
-        # where the gradient lives now: the zero tensor backward() returned -- adopted as .grad by AccumulateGrad, or still on
-        # its way to it (an early flush: AccumulateGrad then adopts or copies the FILLED tensor, stream-ordered) -- unless
-        # AccumulateGrad already made a copy of it (then .grad is another tensor and receives the launch)
-        tw = _from_alias(aw)
-        if w.grad is not None and w.grad.data_ptr() != tw.data_ptr():
-            tw = w.grad.view(-1)
-        tb = None
-        if fused_b:
-            tb = _from_alias(ab)
-            if b.grad is not None and b.grad.data_ptr() != tb.data_ptr():
-                tb = b.grad.view(-1)
-        if not tw.is_contiguous() or tw.dtype != torch.float32 or (tb is not None and not tb.is_contiguous()):
-            raise RuntimeError("deferred weight gradient: .grad must be a contiguous fp32 tensor")
-        descs += _lin_wgrad_descs(x, dy, spec, tw, tb)
+        descs += _lin_wgrad_descs(x, dy, spec, _grad_target(w, aw), _grad_target(b, ab) if fused_b else None)
     if descs:
         _defer_stats["flushes"] += 1
         _gemm_group(descs, _stream())
@@ -695,8 +667,10 @@ def _launch_queue(q, early=False):
 
 
 def _grad_target(p, a):
-    """where a queued gradient of parameter p lives now: the zero tensor backward() returned (alias a), unless AccumulateGrad
-    made a copy of it or summed several contributions -- then .grad is another tensor and receives the launch"""
+    """where a queued gradient of parameter p lives now: the zero tensor backward() returned (alias a) -- adopted as .grad by
+    AccumulateGrad, or still on its way to it (an early flush: AccumulateGrad then adopts or copies the FILLED tensor,
+    stream-ordered) -- unless AccumulateGrad made a copy of it or summed several contributions: then .grad is another tensor
+    and receives the launch"""
     t = _from_alias(a)
     if p.grad is not None and p.grad.data_ptr() != t.data_ptr():
         t = p.grad.view(-1)
@@ -1102,9 +1076,13 @@ class _Gate(Function):
             return _GateBwd.apply(x, dy, S, gated_layout, c_silu, c_sig), None, None, None, None
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
-        call("eqf_gate_bwd", _p(x), _p(dy), _p(dx), x.shape[0], S, gated_layout.c_ref, c_silu, c_sig, _stream())
-        return dx, None, None, None, None
+        return _gate_bwd(x, dy, *ctx.args), None, None, None, None
+
+
+def _gate_bwd(x, dy, S, gated_layout, c_silu, c_sig):
+    dx = torch.empty_like(x)
+    call("eqf_gate_bwd", _p(x), _p(dy), _p(dx), x.shape[0], S, gated_layout.c_ref, c_silu, c_sig, _stream())
+    return dx
 
 
 class _GateBwd(Function):
@@ -1112,11 +1090,9 @@ class _GateBwd(Function):
     def forward(ctx, x, dy, S, gated_layout, c_silu, c_sig):
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
-        call("eqf_gate_bwd", _p(x), _p(dy), _p(dx), x.shape[0], S, gated_layout.c_ref, c_silu, c_sig, _stream())
         ctx.save_for_backward(x, dy)
         ctx.args = (S, gated_layout, c_silu, c_sig)
-        return dx
+        return _gate_bwd(x, dy, *ctx.args)
 
     @staticmethod
     @once_differentiable
@@ -1153,9 +1129,13 @@ class _ScaledSilu(Function):
             return _ScaledSiluBwd.apply(x, dy, ctx.c), None
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
-        call("eqf_silu_bwd", _p(x), _p(dy), _p(dx), x.numel(), ctx.c, _stream())
-        return dx, None
+        return _silu_bwd(x, dy, ctx.c), None
+
+
+def _silu_bwd(x, dy, c):
+    dx = torch.empty_like(x)
+    call("eqf_silu_bwd", _p(x), _p(dy), _p(dx), x.numel(), c, _stream())
+    return dx
 
 
 class _ScaledSiluBwd(Function):
@@ -1163,11 +1143,9 @@ class _ScaledSiluBwd(Function):
     def forward(ctx, x, dy, c0):
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
-        call("eqf_silu_bwd", _p(x), _p(dy), _p(dx), x.numel(), c0, _stream())
         ctx.save_for_backward(x, dy)
         ctx.c0 = c0
-        return dx
+        return _silu_bwd(x, dy, c0)
 
     @staticmethod
     @once_differentiable
@@ -1207,11 +1185,15 @@ class _LnSilu(Function):
                 None, None
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
-        dg, db = _zeros2(gamma.numel(), beta.numel(), x.device)
-        call("eqf_lnsilu_group_bwd", _p(x), _p(gamma), _p(beta), _p(dy), _p(dx), _p(dg), _p(db), x.shape[0],
-             x.shape[1] // G, G, ctx.eps, _stream())
-        return dx, dg, db, None, None
+        return _ln_silu_bwd(x, gamma, beta, dy, ctx.eps, G) + (None, None)
+
+
+def _ln_silu_bwd(x, gamma, beta, dy, eps, groups):
+    dx = torch.empty_like(x)
+    dg, db = _zeros2(gamma.numel(), beta.numel(), x.device)
+    call("eqf_lnsilu_group_bwd", _p(x), _p(gamma), _p(beta), _p(dy), _p(dx), _p(dg), _p(db), x.shape[0],
+         x.shape[1] // groups, groups, eps, _stream())
+    return dx, dg, db
 
 
 class _LnSiluBwd(Function):
@@ -1219,10 +1201,7 @@ class _LnSiluBwd(Function):
     def forward(ctx, x, gamma, beta, dy, eps, groups=1):
         dy = _c(dy)
         _chk(dy)
-        dx = torch.empty_like(x)
-        dg, db = _zeros2(gamma.numel(), beta.numel(), x.device)
-        call("eqf_lnsilu_group_bwd", _p(x), _p(gamma), _p(beta), _p(dy), _p(dx), _p(dg), _p(db), x.shape[0],
-             x.shape[1] // groups, groups, eps, _stream())
+        dx, dg, db = _ln_silu_bwd(x, gamma, beta, dy, eps, groups)
         ctx.save_for_backward(x, gamma, beta, dy)
         ctx.eps, ctx.groups = eps, groups
         if not _want_param_grads():
@@ -1630,8 +1609,7 @@ def _gather_add_bwd(dmsg, g, n, want_a, want_b):
         da = torch.empty((n, D), device=dmsg.device, dtype=torch.float32)
         call("eqf_segment_sum", _p(dmsg), _p(g.src_ptr), _p(g.src_perm), _p(da), n, D, 1.0, 0, st)
     if want_b:
-        db = torch.empty((n, D), device=dmsg.device, dtype=torch.float32)
-        call("eqf_segment_sum", _p(dmsg), _p(g.row_ptr), None, _p(db), n, D, 1.0, 0, st)
+        db = _segment_sum(dmsg, g.row_ptr, n, 1.0)
     return da, db
 
 
@@ -1692,6 +1670,18 @@ def gather_add(a, b, graph):
     return _GatherAdd.apply(a, b, graph)
 
 
+def _segment_sum(x, ptr, nseg, scale):
+    out = torch.empty((nseg, x.shape[1]), device=x.device, dtype=torch.float32)
+    call("eqf_segment_sum", _p(x), _p(ptr), None, _p(out), nseg, x.shape[1], scale, 0, _stream())
+    return out
+
+
+def _segment_bcast(dout, seg_of, n, scale):
+    dx = torch.empty((n, dout.shape[1]), device=dout.device, dtype=torch.float32)
+    call("eqf_segment_bcast", _p(dout), _p(seg_of), _p(dx), n, dout.shape[1], scale, _stream())
+    return dx
+
+
 class _SegmentBcast(Function):
     """dx[q] = scale * dout[seg_of[q]] as a differentiable (linear) op; create_graph only."""
 
@@ -1699,23 +1689,18 @@ class _SegmentBcast(Function):
     def forward(ctx, dout, seg_of, ptr, n, scale):
         dout = _c(dout)
         _chk(dout)
-        D = dout.shape[1]
-        dx = torch.empty((n, D), device=dout.device, dtype=torch.float32)
-        call("eqf_segment_bcast", _p(dout), _p(seg_of), _p(dx), n, D, scale, _stream())
         ctx.save_for_backward(ptr)
-        ctx.args = (dout.shape[0], D, scale)
-        return dx
+        ctx.args = (dout.shape[0], scale)
+        return _segment_bcast(dout, seg_of, n, scale)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, c):
         (ptr,) = ctx.saved_tensors
-        nseg, D, scale = ctx.args
+        nseg, scale = ctx.args
         c = _c(c)
         _chk(c)
-        out = torch.empty((nseg, D), device=c.device, dtype=torch.float32)
-        call("eqf_segment_sum", _p(c), _p(ptr), None, _p(out), nseg, D, scale, 0, _stream())
-        return out, None, None, None, None
+        return _segment_sum(c, ptr, nseg, scale), None, None, None, None
 
 
 class _SegmentSum(Function):
@@ -1723,24 +1708,19 @@ class _SegmentSum(Function):
     def forward(ctx, x, ptr, seg_of, nseg, scale):
         x = _c(x)
         _chk(x, ptr, seg_of)
-        D = x.shape[1]
-        out = torch.empty((nseg, D), device=x.device, dtype=torch.float32)
-        call("eqf_segment_sum", _p(x), _p(ptr), None, _p(out), nseg, D, scale, 0, _stream())
         ctx.save_for_backward(seg_of, ptr)
-        ctx.args = (x.shape[0], D, scale)
-        return out
+        ctx.args = (x.shape[0], scale)
+        return _segment_sum(x, ptr, nseg, scale)
 
     @staticmethod
     def backward(ctx, dout):
         seg_of, ptr = ctx.saved_tensors
-        n, D, scale = ctx.args
+        n, scale = ctx.args
         if torch.is_grad_enabled():  # create_graph
             return _SegmentBcast.apply(dout, seg_of, ptr, n, scale), None, None, None, None
         dout = _c(dout)
         _chk(dout)
-        dx = torch.empty((n, D), device=dout.device, dtype=torch.float32)
-        call("eqf_segment_bcast", _p(dout), _p(seg_of), _p(dx), n, D, scale, _stream())
-        return dx, None, None, None, None
+        return _segment_bcast(dout, seg_of, n, scale), None, None, None, None
 
 
 def segment_sum(x, ptr, seg_of, nseg, scale=1.0):
@@ -1800,11 +1780,15 @@ class _EdgeGeom(Function):
 
 
 def _edge_geom_dpos(vec, dsh, dlen, g, lmax, n):
-    st = _stream()
     dvec = torch.empty_like(vec)
-    call("eqf_edge_geom_bwd", _p(vec), _p(dsh), _p(dlen), g.E, lmax, _p(dvec), st)
-    # d pos[n] = sum_{src(e)=n} dvec[e] - sum_{dst(e)=n} dvec[e]   (segmented, no atomics)
-    dpos = torch.empty((n, 3), device=vec.device, dtype=torch.float32)
+    call("eqf_edge_geom_bwd", _p(vec), _p(dsh), _p(dlen), g.E, lmax, _p(dvec), _stream())
+    return _src_minus_dst(dvec, g, n)
+
+
+def _src_minus_dst(dvec, g, n):
+    """d pos[n] = sum_{src(e)=n} dvec[e] - sum_{dst(e)=n} dvec[e]   (segmented, no atomics)"""
+    st = _stream()
+    dpos = torch.empty((n, 3), device=dvec.device, dtype=torch.float32)
     call("eqf_segment_sum", _p(dvec), _p(g.src_ptr), _p(g.src_perm), _p(dpos), n, 3, 1.0, 0, st)
     call("eqf_segment_sum", _p(dvec), _p(g.row_ptr), None, _p(dpos), n, 3, -1.0, 1, st)
     return dpos
@@ -1840,10 +1824,7 @@ class _EdgeGeomBwd(Function):
         g_dsh = torch.empty_like(dsh) if dsh is not None else None
         g_dlen = torch.empty_like(dlen) if dlen is not None else None
         call("eqf_edge_geom_bwd2", _p(vec), _p(dsh), _p(dlen), _p(c_vec), E, lmax, _p(g_vec), _p(g_dsh), _p(g_dlen), st)
-        g_pos = torch.empty((n, 3), device=vec.device, dtype=torch.float32)
-        call("eqf_segment_sum", _p(g_vec), _p(g.src_ptr), _p(g.src_perm), _p(g_pos), n, 3, 1.0, 0, st)
-        call("eqf_segment_sum", _p(g_vec), _p(g.row_ptr), None, _p(g_pos), n, 3, -1.0, 1, st)
-        return g_pos, None, g_dlen, g_dsh, None, None
+        return _src_minus_dst(g_vec, g, n), None, g_dlen, g_dsh, None, None
 
 
 def edge_geometry(pos, offsets, graph, lmax):
@@ -2075,10 +2056,14 @@ class _RbfExpNorm(Function):
             return _RbfExpNormBwd.apply(length, dout, means, betas, ctx.args[0], ctx.args[1]), None, None, None, None
         dout = _c(dout)
         _chk(dout)
-        dlen = torch.empty_like(length)
-        call("eqf_rbf_expnorm_bwd", _p(length), _p(dout), length.shape[0], means.numel(), _p(means), _p(betas),
-             ctx.args[0], ctx.args[1], _p(dlen), _stream())
-        return dlen, None, None, None, None
+        return _rbf_expnorm_bwd(length, dout, means, betas, *ctx.args), None, None, None, None
+
+
+def _rbf_expnorm_bwd(length, dout, means, betas, alpha, cutoff):
+    dlen = torch.empty_like(length)
+    call("eqf_rbf_expnorm_bwd", _p(length), _p(dout), length.shape[0], means.numel(), _p(means), _p(betas), alpha,
+         cutoff, _p(dlen), _stream())
+    return dlen
 
 
 class _RbfExpNormBwd(Function):
@@ -2086,12 +2071,9 @@ class _RbfExpNormBwd(Function):
     def forward(ctx, length, dout, means, betas, alpha, cutoff):
         dout = _c(dout)
         _chk(dout)
-        dlen = torch.empty_like(length)
-        call("eqf_rbf_expnorm_bwd", _p(length), _p(dout), length.shape[0], means.numel(), _p(means), _p(betas), alpha,
-             cutoff, _p(dlen), _stream())
         ctx.save_for_backward(length, dout, means, betas)
         ctx.args = (alpha, cutoff)
-        return dlen
+        return _rbf_expnorm_bwd(length, dout, means, betas, alpha, cutoff)
 
     @staticmethod
     @once_differentiable
@@ -2109,15 +2091,20 @@ def rbf_expnorm(length, means, betas, alpha, cutoff):
     return _RbfExpNorm.apply(length, means, betas, float(alpha), float(cutoff))
 
 
+def _rbf_bessel_bwd(length, freq, dout, cutoff, want_len=True, want_freq=True):
+    dlen = torch.empty_like(length) if want_len else None
+    dfreq = _zeros_like(freq) if want_freq else None
+    call("eqf_rbf_bessel_bwd", _p(length), _p(dout), length.shape[0], freq.numel(), _p(freq), cutoff, _p(dfreq),
+         _p(dlen), _stream())
+    return dlen, dfreq
+
+
 class _RbfBesselBwd(Function):
     @staticmethod
     def forward(ctx, length, freq, dout, cutoff):
         dout = _c(dout)
         _chk(dout)
-        dlen = torch.empty_like(length)
-        dfreq = _zeros_like(freq)
-        call("eqf_rbf_bessel_bwd", _p(length), _p(dout), length.shape[0], freq.numel(), _p(freq), cutoff, _p(dfreq),
-             _p(dlen), _stream())
+        dlen, dfreq = _rbf_bessel_bwd(length, freq, dout, cutoff)
         ctx.save_for_backward(length, freq, dout)
         ctx.cutoff = cutoff
         if not _want_param_grads():
@@ -2157,11 +2144,8 @@ class _RbfBessel(Function):
             return dlen, _guard(dfreq, (dout, length, freq), "Bessel frequency gradient"), None
         dout = _c(dout)
         _chk(dout)
-        dlen = torch.empty_like(length) if ctx.needs_input_grad[0] else None
-        dfreq = _zeros_like(freq) if (ctx.needs_input_grad[1] and _want_param_grads()) else None
-        call("eqf_rbf_bessel_bwd", _p(length), _p(dout), length.shape[0], freq.numel(), _p(freq), ctx.cutoff, _p(dfreq),
-             _p(dlen), _stream())
-        return dlen, dfreq, None
+        return _rbf_bessel_bwd(length, freq, dout, ctx.cutoff, ctx.needs_input_grad[0],
+                               ctx.needs_input_grad[1] and _want_param_grads()) + (None,)
 
 
 def rbf_bessel(length, freq, cutoff):
@@ -2231,12 +2215,9 @@ class _Dtp(Function):
         x, coupling = _c(x), _c(coupling)
         w = _c(w) if w is not None else None
         _chk(x, coupling, w)
-        E = x.shape[0]
-        out = torch.empty((E, table.layout_out.dim), device=x.device, dtype=torch.float32)
-        call("eqf_dtp_fwd", _p(x), _p(coupling), _p(w), table.c_ref, _p(out), E, _stream())
         ctx.save_for_backward(x, coupling, w)
         ctx.table = table
-        return out
+        return _dtp_fwd(x, coupling, w, table)
 
     @staticmethod
     def backward(ctx, dout):
@@ -2357,9 +2338,7 @@ class _DtpLinear(Function):
         E = x.shape[0]
         assert weight.numel() == spec.weight_numel
         out = torch.empty((E, spec.out_layout.dim), device=x.device, dtype=torch.float32)
-        Wl = (ctypes.c_void_p * 8)()
-        for (l3, K, N, w_off, _, _, slot) in spec.blocks:
-            Wl[slot] = weight.data_ptr() + 4 * w_off
+        Wl = _ptr_array((slot, weight.data_ptr() + 4 * w_off) for (_, _, _, w_off, _, _, slot) in spec.blocks)
         call("eqf_dtp_linear_fwd", _p(x), _p(coupling), _p(w), spec.table.c_ref, Wl, _p(bias), _p(out),
              spec.out_layout.c_ref, E, _stream())
         ctx.save_for_backward(x, coupling, w, weight)
@@ -2387,19 +2366,14 @@ class _DtpLinear(Function):
                 d = 2 * l3 + 1
                 call("eqf_gemm_nt", _p(dout, out_off), rows(d, Dout, N), _p(weight, w_off), N, _p(dmid, mid_off),
                      rows(d, Dmid, K), None, E * d, K, N, 0, st)
-            dx = torch.empty_like(x) if table.in_covered else _zeros_like(x)
-            dw = torch.empty_like(w) if (w is not None and ctx.needs_input_grad[2]) else None
-            dM = torch.empty_like(coupling) if ctx.needs_input_grad[1] else None
-            call("eqf_dtp_bwd", _p(x), _p(coupling), _p(w), table.c_ref, _p(dmid), _p(dx), _p(dw), _p(dM), E, st)
+            dx, dM, dw = _dtp_bwd(x, coupling, w, dmid, table, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
             del dmid
         want_b = ctx.has_bias and ctx.needs_input_grad[4]
         if ctx.needs_input_grad[3] or want_b:
             dweight_, dbias_ = _zeros2(weight.numel(), spec.bias_dim if want_b else 0, x.device)
         if ctx.needs_input_grad[3]:
             dweight = dweight_
-            dWl = (ctypes.c_void_p * 8)()
-            for (l3, K, N, w_off, _, _, slot) in spec.blocks:
-                dWl[slot] = dweight.data_ptr() + 4 * w_off
+            dWl = _ptr_array((slot, dweight.data_ptr() + 4 * w_off) for (_, _, _, w_off, _, _, slot) in spec.blocks)
             call("eqf_dtp_linear_wgrad", _p(x), _p(coupling), _p(w), table.c_ref, _p(dout), spec.out_layout.c_ref, dWl,
                  E, st)
         if want_b:
@@ -2707,59 +2681,27 @@ class _SepFctp(Function):
     def backward(ctx, d1, d2=None):
         x, coupling, w, weight, weight2 = ctx.saved_tensors
         spec = ctx.spec
-        E = x.shape[0]
-        st = _stream()
         dev = x.device
-        if torch.is_grad_enabled():  # create_graph: differentiable data-gradient (forces); see _SepFctpBwdData
-            need = ctx.needs_input_grad
-            if d1 is None:
-                d1 = _zeros((E, spec.out_layout.dim), device=dev, dtype=torch.float32)
-            if spec.n2 and d2 is None:
-                d2 = _zeros((E, spec.n2), device=dev, dtype=torch.float32)
-            outs = _SepFctpBwdData.apply(x, coupling, w, weight, weight2, d1, d2 if spec.n2 else None, spec, ctx.mode,
-                                         ctx.packed)
-            dx, dM = outs[0], outs[1]
-            dw = outs[2] if w is not None else None
-            # needs_input_grad is static (the parameters always "need" a gradient), so the weight / bias gradients
-            # are produced here as well -- first-order kernels, guarded: differentiating THROUGH them is not implemented
-            gW = gb = gW2 = gb2 = None
-            if not _want_param_grads():
-                return dx, dM, dw, None, None, None, None, None
-            if need[3] or need[5]:
-                with torch.no_grad():
-                    gW_ = _zeros_like(weight)
-                    gW2_ = _zeros_like(weight2) if weight2 is not None else None
-                    _sfc_bwd_weight(x, coupling, w, _c(d1), _c(d2) if spec.n2 else None, spec, gW_, gW2_, ctx.mode)
-                deps = (d1, d2, x, coupling, w)
-                gW = _guard(gW_, deps, "weight gradient of the fused SeparableFCTP")
-                gW2 = _guard(gW2_, deps, "weight gradient of the fused SeparableFCTP") if gW2_ is not None else None
-            if ctx.has_bias[0] and need[4]:
-                j = spec.out_layout.seg_index(0)
-                o = spec.out_layout.offsets[j]
-                gb = d1[:, o:o + spec.out_layout.mul_of(0)].sum(0)
-            if ctx.has_bias[1] and need[6]:
-                gb2 = d2.sum(0)
-            return dx, dM, dw, gW, gb, gW2, gb2, None
-        if d1 is None:
-            d1 = _zeros((E, spec.out_layout.dim), device=dev, dtype=torch.float32)
-        if spec.n2 and d2 is None:
-            d2 = _zeros((E, spec.n2), device=dev, dtype=torch.float32)
-        d1 = _c(d1)
-        d2 = _c(d2) if spec.n2 else None
-        _chk(d1, d2)
         need = ctx.needs_input_grad
-        dx = dM = dw = dweight = dbias = dweight2 = dbias2 = None
         want_b = ctx.has_bias[0] and need[4]
         want_b2 = ctx.has_bias[1] and need[6]
+        d1, d2 = _sfc_cotangents(d1, d2, spec, x)
+        if torch.is_grad_enabled():  # create_graph: differentiable data-gradient (forces); see _SepFctpBwdData
+            outs = _SepFctpBwdData.apply(x, coupling, w, weight, weight2, d1, d2, spec, ctx.mode, ctx.packed)
+            dx, dM = outs[0], outs[1]
+            dw = outs[2] if w is not None else None
+            if not _want_param_grads():
+                return dx, dM, dw, None, None, None, None, None
+            gW, gb, gW2, gb2 = _sfc_param_grads_guarded(x, coupling, w, weight, weight2, d1, d2, spec, ctx.mode,
+                                                        need[3] or need[5], want_b, want_b2, (d1, d2, x, coupling, w))
+            return dx, dM, dw, gW, gb, gW2, gb2, None
+        d1 = _c(d1)
+        d2 = _c(d2) if d2 is not None else None
+        _chk(d1, d2)
+        dx = dM = dw = dweight = dbias = dweight2 = dbias2 = None
         want_w = _want_param_grads() and (need[3] or need[5] or want_b or want_b2)
-        flat = None
         if want_w:
-            n1_0 = spec.out_layout.mul_of(0)
-            sizes = [spec.weight_numel, spec.weight2_numel, n1_0 if want_b else 0, spec.n2 if want_b2 else 0]
-            flat = _zeros(sum(sizes), device=dev, dtype=torch.float32)  # ONE fill for every accumulated gradient
-            o1, o2, o3 = sizes[0], sizes[0] + sizes[1], sizes[0] + sizes[1] + sizes[2]
-            dweight = flat[:o1]
-            dweight2 = flat[o1:o2] if spec.n2 else None
+            dweight, dweight2, dbias, dbias2 = _sfc_accumulators(spec, dev, want_b, want_b2)
         # The weight gradient and the data gradient read the same tensors and write disjoint ones: the weight gradient goes
         # out on a side stream and runs beside the data gradient (both kernels leave most of a SIMD's issue slots idle --
         # their waves wait on memory > 50 % of the time, profiles/r03 -- so the two overlap instead of queueing).
@@ -2773,22 +2715,62 @@ class _SepFctp(Function):
             dx, dM, dw = _sfc_bwd_data(x, coupling, w, weight, weight2, d1, d2, spec, need[1], ctx.mode, ctx.packed)
         if side is not None:
             torch.cuda.current_stream(dev).wait_stream(side)
-        if not _want_param_grads():  # force evaluation
-            return dx, dM, dw, None, None, None, None, None
         if want_w:
-            dbias = flat[o2:o3] if want_b else None
-            dbias2 = flat[o3:] if want_b2 else None
             bias_done = False
             if side is None and (need[3] or need[5]):
                 # (the bias gradients ride along in the weight-gradient launch: its degree-0 items stream those columns anyway)
                 bias_done = _sfc_bwd_weight(x, coupling, w, d1, d2, spec, dweight, dweight2, ctx.mode, dbias, dbias2)
-            if want_b and not bias_done:
-                j = spec.out_layout.seg_index(0)
-                call("eqf_colsum", _p(d1, spec.out_layout.offsets[j]), rows(1, spec.out_layout.dim, 0), E, n1_0,
-                     _p(dbias), st)
-            if want_b2 and not bias_done:
-                call("eqf_colsum", _p(d2), rows(1, spec.n2, 0), E, spec.n2, _p(dbias2), st)
+            if not bias_done:
+                _sfc_bias_colsum(d1, d2, spec, dbias, dbias2)
         return dx, dM, dw, dweight, dbias, dweight2, dbias2, None
+
+
+# What the backward of the fused operator and of its gated form share.
+def _sfc_cotangents(d1, d2, spec, x):
+    """(d1, d2) with a cotangent that did not arrive materialised as zeros; d2 is None without a second consumer"""
+    if d1 is None:
+        d1 = _zeros((x.shape[0], spec.out_layout.dim), device=x.device, dtype=torch.float32)
+    if spec.n2 and d2 is None:
+        d2 = _zeros((x.shape[0], spec.n2), device=x.device, dtype=torch.float32)
+    return d1, (d2 if spec.n2 else None)
+
+
+def _sfc_param_grads_guarded(x, coupling, w, weight, weight2, d1, d2, spec, mode, want_w, want_b, want_b2, deps):
+    """(gW, gb, gW2, gb2) of a create_graph backward: needs_input_grad is static (the parameters always "need" a gradient), so
+    the weight / bias gradients are produced there as well -- the weights' by the first-order kernel, guarded (differentiating
+    THROUGH them is not implemented), the biases' as ATen column sums."""
+    gW = gb = gW2 = gb2 = None
+    if want_w:
+        with torch.no_grad():
+            gW = _zeros_like(weight)
+            gW2 = _zeros_like(weight2) if weight2 is not None else None
+            _sfc_bwd_weight(x, coupling, w, _c(d1), _c(d2) if d2 is not None else None, spec, gW, gW2, mode)
+        gW = _guard(gW, deps, "weight gradient of the fused SeparableFCTP")
+        gW2 = _guard(gW2, deps, "weight gradient of the fused SeparableFCTP")
+    if want_b:
+        o = spec.out_layout.offsets[spec.out_layout.seg_index(0)]
+        gb = d1[:, o:o + spec.out_layout.mul_of(0)].sum(0)
+    if want_b2:
+        gb2 = d2.sum(0)
+    return gW, gb, gW2, gb2
+
+
+def _sfc_accumulators(spec, dev, want_b, want_b2):
+    """(dweight, dweight2, dbias, dbias2): slices of ONE zero-filled buffer, one fill for every accumulated gradient"""
+    sizes = [spec.weight_numel, spec.weight2_numel, spec.out_layout.mul_of(0) if want_b else 0, spec.n2 if want_b2 else 0]
+    flat = _zeros(sum(sizes), device=dev, dtype=torch.float32)
+    o1, o2, o3 = sizes[0], sizes[0] + sizes[1], sizes[0] + sizes[1] + sizes[2]
+    return flat[:o1], (flat[o1:o2] if spec.n2 else None), (flat[o2:o3] if want_b else None), (flat[o3:] if want_b2 else None)
+
+
+def _sfc_bias_colsum(d1, d2, spec, dbias, dbias2):
+    """the bias gradients no weight-gradient launch took along: column sums of the 0e block of d1 / of d2"""
+    lay = spec.out_layout
+    if dbias is not None:
+        call("eqf_colsum", _p(d1, lay.offsets[lay.seg_index(0)]), rows(1, lay.dim, 0), d1.shape[0], lay.mul_of(0), _p(dbias),
+             _stream())
+    if dbias2 is not None:
+        call("eqf_colsum", _p(d2), rows(1, spec.n2, 0), d2.shape[0], spec.n2, _p(dbias2), _stream())
 
 
 class _SepFctpGated(Function):
@@ -2826,25 +2808,18 @@ class _SepFctpGated(Function):
         spec, mode = ctx.spec, ctx.mode
         S, gated_layout, c_silu, c_sig = ctx.gate
         need = ctx.needs_input_grad  # x_raw, coupling, w, weight, bias
+        want_b = ctx.has_bias and need[4]
         E = x_raw.shape[0]
-        dev = x_raw.device
         if torch.is_grad_enabled():  # create_graph: the separate differentiable operators, on the re-materialised gate output
             xg = gate(x_raw, S, gated_layout, c_silu, c_sig)
             outs = _SepFctpBwdData.apply(xg, coupling, w, weight, None, d1, None, spec, mode, ctx.packed)
             dxg, dM = outs[0], outs[1]
             dw = outs[2] if w is not None else None
             dx_raw = _GateBwd.apply(x_raw, dxg, S, gated_layout, c_silu, c_sig) if need[0] else None
-            gW = gb = None
             if not _want_param_grads():
                 return dx_raw, dM, dw, None, None, None, None
-            if need[3]:
-                with torch.no_grad():
-                    gW_ = _zeros_like(weight)
-                    _sfc_bwd_weight(xg.detach(), coupling, w, _c(d1), None, spec, gW_, None, mode)
-                gW = _guard(gW_, (d1, x_raw, coupling, w), "weight gradient of the fused SeparableFCTP")
-            if ctx.has_bias and need[4]:
-                o = spec.out_layout.offsets[spec.out_layout.seg_index(0)]
-                gb = d1[:, o:o + spec.out_layout.mul_of(0)].sum(0)
+            gW, gb, _, _ = _sfc_param_grads_guarded(xg.detach(), coupling, w, weight, None, d1, None, spec, mode, need[3],
+                                                    want_b, False, (d1, x_raw, coupling, w))
             return dx_raw, dM, dw, gW, gb, None, None
         d1 = _c(d1)
         _chk(d1)
@@ -2858,18 +2833,13 @@ class _SepFctpGated(Function):
                  ctypes.c_void_p(ctx.packed.data_ptr()), _p(d1), spec.out_layout.c_ref, _p(dx_raw), _p(dw), _p(dM), E, mode, st)
         if not _want_param_grads():
             return dx_raw, dM, dw, None, None, None, None
-        want_b = ctx.has_bias and need[4]
         if need[3] or want_b:
-            n1_0 = spec.out_layout.mul_of(0)
-            flat = _zeros(spec.weight_numel + (n1_0 if want_b else 0), device=dev, dtype=torch.float32)
-            dweight = flat[:spec.weight_numel]
-            dbias = flat[spec.weight_numel:] if want_b else None
+            dweight, _, dbias, _ = _sfc_accumulators(spec, x_raw.device, want_b, False)
             if need[3]:
                 call("eqf_sfcx_bwd_weight_gated_bias", _p(x_raw), ctypes.byref(ctx.gin), _p(coupling), _p(w), spec.table.c_ref,
                      _p(d1), spec.out_layout.c_ref, _sfc_Wl(dweight, spec), _p(dbias), E, mode, st)
-            elif want_b:
-                o = spec.out_layout.offsets[spec.out_layout.seg_index(0)]
-                call("eqf_colsum", _p(d1, o), rows(1, spec.out_layout.dim, 0), E, n1_0, _p(dbias), st)
+            else:
+                _sfc_bias_colsum(d1, None, spec, dbias, None)
         return dx_raw, dM, dw, (dweight if need[3] else None), dbias, None, None
 
 
@@ -2926,10 +2896,14 @@ class _AlphaLogits(Function):
             return da, _guard(dd, (dlogit, a), "alpha_dot gradient"), None, None, None
         dlogit = _c(dlogit)
         _chk(dlogit)
-        da = torch.empty_like(a)
-        dd = _zeros_like(alpha_dot)
-        call("eqf_alpha_bwd", _p(a), _p(alpha_dot), _p(dlogit), _p(da), _p(dd), a.shape[0], H, Kh, c, _stream())
-        return da, dd, None, None, None
+        return _alpha_bwd(a, alpha_dot, dlogit, H, Kh, c) + (None, None, None)
+
+
+def _alpha_bwd(a, alpha_dot, dlogit, H, Kh, c):
+    da = torch.empty_like(a)
+    dd = _zeros_like(alpha_dot)
+    call("eqf_alpha_bwd", _p(a), _p(alpha_dot), _p(dlogit), _p(da), _p(dd), a.shape[0], H, Kh, c, _stream())
+    return da, dd
 
 
 class _AlphaLogitsBwd(Function):
@@ -2937,9 +2911,7 @@ class _AlphaLogitsBwd(Function):
     def forward(ctx, a, alpha_dot, dlogit, H, Kh, c):
         dlogit = _c(dlogit)
         _chk(dlogit)
-        da = torch.empty_like(a)
-        dd = _zeros_like(alpha_dot)
-        call("eqf_alpha_bwd", _p(a), _p(alpha_dot), _p(dlogit), _p(da), _p(dd), a.shape[0], H, Kh, c, _stream())
+        da, dd = _alpha_bwd(a, alpha_dot, dlogit, H, Kh, c)
         ctx.save_for_backward(a, alpha_dot, dlogit)
         ctx.args = (H, Kh, c)
         if not _want_param_grads():
@@ -3013,15 +2985,20 @@ class _AttnAggregate(Function):
             return dlogit, dvalue, None, None, None, None, None
         dout = _c(dout)
         _chk(dout)
-        dvalue = torch.empty_like(value)
-        dlogit = torch.empty_like(alpha)
-        if ctx.seed_off is None:
-            call("eqf_attn_aggregate_bwd", _p(alpha), _p(value), _p(graph.row_ptr), _p(dout), _p(dvalue), _p(dlogit),
-                 graph.N, H, layout.c_ref, drop_p, seed, _stream())
-        else:
-            call("eqf_attn_aggregate_bwd_dseed", _p(alpha), _p(value), _p(graph.row_ptr), _p(dout), _p(dvalue), _p(dlogit),
-                 graph.N, H, layout.c_ref, drop_p, seed, _p(ctx.seed_off), _stream())
-        return dlogit, dvalue, None, None, None, None, None
+        return _attn_aggregate_bwd(alpha, value, dout, *ctx.args, ctx.seed_off) + (None, None, None, None, None)
+
+
+def _attn_aggregate_bwd(alpha, value, dout, graph, H, layout, drop_p, seed, seed_off=None):
+    """(d_logit, d_value): first order; seed_off: the device word of a captured step (dropout_seed_offset)"""
+    dvalue = torch.empty_like(value)
+    dlogit = torch.empty_like(alpha)
+    if seed_off is None:
+        call("eqf_attn_aggregate_bwd", _p(alpha), _p(value), _p(graph.row_ptr), _p(dout), _p(dvalue), _p(dlogit),
+             graph.N, H, layout.c_ref, drop_p, seed, _stream())
+    else:
+        call("eqf_attn_aggregate_bwd_dseed", _p(alpha), _p(value), _p(graph.row_ptr), _p(dout), _p(dvalue), _p(dlogit),
+             graph.N, H, layout.c_ref, drop_p, seed, _p(seed_off), _stream())
+    return dlogit, dvalue
 
 
 class _AttnAggregateBwd(Function):
@@ -3032,13 +3009,9 @@ class _AttnAggregateBwd(Function):
     def forward(ctx, logit, value, dout, alpha, graph, H, layout, drop_p, seed):
         dout = _c(dout)
         _chk(dout)
-        dvalue = torch.empty_like(value)
-        dlogit = torch.empty_like(alpha)
-        call("eqf_attn_aggregate_bwd", _p(alpha), _p(value), _p(graph.row_ptr), _p(dout), _p(dvalue), _p(dlogit),
-             graph.N, H, layout.c_ref, drop_p, seed, _stream())
         ctx.save_for_backward(alpha, value, dout)
         ctx.args = (graph, H, layout, drop_p, seed)
-        return dlogit, dvalue
+        return _attn_aggregate_bwd(alpha, value, dout, *ctx.args)
 
     @staticmethod
     @once_differentiable

@@ -206,10 +206,8 @@ int eqf_gemm_nn(const float* A, eqf_rows ra, const float* B, int ldb, float* C, 
 int eqf_gemm_nt(const float* A, eqf_rows ra, const float* B, int ldb, float* C, eqf_rows rc,
                 const float* bias, int M, int N, int K, int accumulate, void* stream);
 /* C[m,n] += sum_i A[i,m] * B[i,n]   over R rows (two-level on both operands); C plain [M,N] with
- * leading dimension ldc.  C is always ACCUMULATED into (split over row chunks with fp32 atomics). */
-int eqf_gemm_tn(const float* A, eqf_rows ra, const float* B, eqf_rows rb, float* C, int ldc, int M,
-                int N, int R, void* stream);
-/* eqf_gemm_tn that also accumulates the column sums of its operands while they are staged (the bias gradient of the
+ * leading dimension ldc.  C is always ACCUMULATED into (split over row chunks with fp32 atomics).
+ * It also accumulates the column sums of its operands while they are staged (the bias gradient of the
  * same linear layer, otherwise a separate eqf_colsum pass over dy): colsum_a[m] += sum_rows A[row, m] and
  * colsum_b[n] += sum_rows B[row, n]; either may be NULL.  In eqf_gemm_group a kind-2 descriptor's `bias` field is the
  * colsum_b accumulator.  [ref: the `.bias` gradients of nn.Linear (radial_func.py) and of LinearRS,
@@ -441,11 +439,9 @@ int eqf_silu_bwd(const float* x, const float* dy, float* dx, long n, float c, vo
  * every reference config).  [ref: nets/radial_func.py:13-36 (nn.LayerNorm + nn.SiLU)] */
 int eqf_lnsilu_fwd(const float* x, const float* gamma, const float* beta, float* y, int rows, int C,
                    float eps, void* stream);
-/* dx written; d_gamma[C], d_beta[C] ACCUMULATED. */
-int eqf_lnsilu_bwd(const float* x, const float* gamma, const float* beta, const float* dy, float* dx,
-                   float* d_gamma, float* d_beta, int rows, int C, float eps, void* stream);
 
-/* The same on a [rows][groups][C] tensor with per-group parameters gamma / beta [groups][C] (d_gamma / d_beta alike):
+/* The same on a [rows][groups][C] tensor with per-group parameters gamma / beta [groups][C] (d_gamma / d_beta alike;
+ * the backward writes dx and ACCUMULATES d_gamma / d_beta):
  * the radial MLPs of all blocks of a model evaluated side by side on the shared radial basis
  * [ref: every TransBlock owns a RadialProfile over the same edge_length_embedding,
  *  nets/graph_attention_transformer.py:200-208,445-447,717 and :880-886]. */
@@ -619,10 +615,7 @@ int eqf_silu_bwd2(const float* x, const float* dy, const float* c, float* g_x, f
 /* c, g_in: [rows, S+G+dim(gated)]; d_out, g_dout: [rows, S+dim(gated)] */
 int eqf_gate_bwd2(const float* in, const float* d_out, const float* c, float* g_in, float* g_dout, int rows, int S,
                   const eqf_irreps* gated, float c_silu, float c_sig, void* stream);
-/* g_gamma[C], g_beta[C] ACCUMULATED */
-int eqf_lnsilu_bwd2(const float* x, const float* gamma, const float* beta, const float* dy, const float* c,
-                    float* g_x, float* g_gamma, float* g_beta, float* g_dy, int rows, int C, float eps, void* stream);
-/* the same on [rows][groups][C] rows with per-group gamma / beta (g_gamma / g_beta [groups][C], ACCUMULATED): the second-order
+/* [rows][groups][C] rows with per-group gamma / beta (g_gamma / g_beta [groups][C], ACCUMULATED): the second-order
  * term of the radial bank -- all RadialProfile MLPs of a model side by side -- when forces are taken with create_graph
  * [ref: nets/radial_func.py:13-36 under nets/graph_attention_transformer_md17.py:318-325] */
 int eqf_lnsilu_group_bwd2(const float* x, const float* gamma, const float* beta, const float* dy, const float* c,
