@@ -25,6 +25,13 @@ int eqf_sfcx_dev_plan(int kind, const eqf_dtp_paths* paths, const eqf_irreps* ou
  *   key 4   weight gradient: 1 = always the one-wave kernel, 2 = the multi-wave kernel (csrc/sfcw.hip) wherever accepted
  *   key 9   data gradient on small graphs: 1 = never split the paths of an item over two waves */
 int eqf_sfcx_dev_set(int key, int value);
+/* which kernel served the last launch of a family (0 forward, 1 data gradient, 2 weight gradient) of the split-precision
+ * entry points; the call clears the record (0: no launch of that family since the last call; other families: EQF_E_BADARG).
+ * Host statics written beside the launch: no kernel is launched and no launch changes.
+ *   forward          1 / 2 / 4 = one-wave kernel, that many waves per item; 8 = multi-wave kernel (csrc/sfcy.hip)
+ *   data gradient    1 = one wave per item, 2 = paths of an item split over two waves, 3 = degree-3 layout (two half passes)
+ *   weight gradient  1 = one-wave kernel, 2 = multi-wave kernel (csrc/sfcw.hip) */
+int eqf_sfcx_dev_served(int family);
 
 #ifdef __cplusplus
 }

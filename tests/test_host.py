@@ -30,6 +30,10 @@ def test_library_exports_every_declared_symbol(hip_lib):
     internal = {n for n in exported if n.startswith("eqf_prof_begin") or n.startswith("eqf_prof_end")}
     assert exported - internal <= declared | dev, sorted(exported - internal - declared - dev)
     assert not (dev & set(lib.SIGNATURES)), "development switches must stay out of the product's binding table"
+    assert {"eqf_sfcx_dev_plan", "eqf_sfcx_dev_set", "eqf_sfcx_dev_served"} <= dev <= exported, sorted(dev - exported)
+    # eqf_sfcx_dev_served reads and clears a host record: a second read reports no launch; other families: EQF_E_BADARG
+    assert all(hip_lib.eqf_sfcx_dev_served(f) in (0, 1, 2, 3, 4, 8) for f in (0, 1, 2))
+    assert [hip_lib.eqf_sfcx_dev_served(f) for f in (0, 1, 2)] == [0, 0, 0] and hip_lib.eqf_sfcx_dev_served(3) == -1
 
 
 def test_binding_table_matches_header_prototypes():
