@@ -17,6 +17,12 @@ What stays OUTSIDE the graph, and why:
   * three numbers the captured launches read from device words instead of frozen by-value arguments: the seed offset of
     the attention dropout (a fresh draw per replay: eqf_attn_aggregate_*_dseed) and {lr, 1 - b1^t, sqrt(1 - b2^t)} of AdamW
     (eqf_adamw_step_dev); the host writes them (pinned buffer, asynchronous copy) before it launches the graph.
+  * per-graph stochastic depth (`drop_path_rate > 0`) likewise: the step classes run every step, eager or captured, inside
+    `droppath.device_draws(word)`, so GraphDropPath draws its keep mask in the kernel (eqf_segment_droppath) from a second
+    device word that holds `dens.step_seed(drop_path_seed, k)` during step k of the instance -- a fresh mask per replay, the
+    same masks as an eager loop under `device_draws(step_seed(drop_path_seed, k))`, padded or not (the draw of a graph does not
+    depend on the number of graphs).  `drop_path_seed=None` draws the base seed from torch's CPU generator when the first
+    GraphDropPath runs; a model without stochastic depth consumes nothing.
 
 The MD17 force-loss step (forces by a create_graph backward inside the forward, then a second-order backward) is captured the
 same way (tests/test_gpu_capture.py; bench.py --workload md17_l2: 463 -> 619 frames/s, md17_l3: 218 -> 254).  The OC20 step on
@@ -28,9 +34,51 @@ attention dropout together with a create_graph backward (no model of the referen
 positions only (an edge list that comes from outside -- OC20 with otf_graph=False -- is sorted by EdgeGraph.from_edges with a
 device sort on the host side of the step: eager), inputs other than the graph at fixed addresses (`forward_loss` reads the same
 tensors every step; copy a new batch into them)."""
+import contextlib
+
 import torch
 
-from . import ops
+from . import droppath, ops
+
+
+class _DropPathWord:
+    """The stochastic-depth seed of a step class: a device word that holds `dens.step_seed(seed, k)` during step k (k counts the
+    steps of the instance from 0), written through a pinned buffer by an asynchronous copy.  seed None: the word holds
+    `step_seed(0, k)` and the base seed travels by value (a constant: a capture may freeze it), drawn from torch's CPU generator
+    by the first GraphDropPath that really runs under the instance -- a model without stochastic depth consumes nothing."""
+
+    def __init__(self, seed, device):
+        self.seed = None if seed is None else int(seed)
+        self.dev = torch.zeros(1, dtype=torch.int64, device=device)
+        self.host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self.k = 0
+        self._drawn = None
+
+    def base(self):
+        if self._drawn is None:
+            self._drawn = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator, as the eager layers draw theirs
+        return self._drawn
+
+    def advance(self):
+        """the word of the next step goes out (the graph build's host read-back follows and waits for it: the pinned buffer is
+        free again when the next step writes it)"""
+        from .dens import step_seed  # (dens imports this module)
+        v = step_seed(self.seed or 0, self.k)
+        self.k += 1
+        self.host[0] = v - (1 << 64) if v >= (1 << 63) else v  # the same 64 bits inside int64's signed range
+        self.dev.copy_(self.host, non_blocking=True)
+
+    def scope(self):
+        return droppath.device_draws(self.dev, base=0 if self.seed is not None else self.base)
+
+
+def _advance(word):
+    if word is not None:
+        word.advance()
+
+
+def _scope(word):
+    return word.scope() if word is not None else contextlib.nullcontext()
 
 
 class CapturedTrainStep:
@@ -41,9 +89,11 @@ class CapturedTrainStep:
     EdgeGraph of this step's batch (`EdgeGraph.from_radius(pos, batch, r, into=into)`, or for periodic structures
     `EdgeGraph.from_radius_pbc(pos, cell, batch, r, k, into=into)[0]`, whose `.offsets` forward_loss passes on), called OUTSIDE
     the capture.
-    optimizer: a FlatAdamW without a reducer."""
+    optimizer: a FlatAdamW without a reducer.  drop_path_seed: the stochastic-depth seed (module docstring; None: drawn)."""
 
-    def __init__(self, optimizer, forward_loss, min_eager=3, max_graphs=4):
+    _drop_path = None  # the _DropPathWord the constructor makes (an instance built without it draws on the host, as before)
+
+    def __init__(self, optimizer, forward_loss, min_eager=3, max_graphs=4, drop_path_seed=None):
         if getattr(optimizer, "_reducer", None) is not None:
             raise ValueError("CapturedTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
         self.opt, self.forward_loss = optimizer, forward_loss
@@ -53,14 +103,16 @@ class CapturedTrainStep:
         dev = optimizer.flat_p.device
         self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self._drop_path = _DropPathWord(drop_path_seed, dev)
         self.replays = self.eager_steps = 0
 
     # ---- one eager step (also what a captured graph records) -------------------------------------------------------
     def _run(self, g):
-        self.opt.zero_grad(set_to_none=True)
-        loss = self.forward_loss(g)
-        loss.backward()
-        self.opt.step()
+        with _scope(self._drop_path):  # (eager steps and the capture alike: one sequence of stochastic-depth masks)
+            self.opt.zero_grad(set_to_none=True)
+            loss = self.forward_loss(g)
+            loss.backward()
+            self.opt.step()
         # detached: a caller that keeps the loss of an EAGER step must not keep that step's autograd graph alive into a later
         # capture (hipStreamEndCapture crashed with one alive, round 6)
         return loss.detach()
@@ -70,6 +122,7 @@ class CapturedTrainStep:
         self._seed_dev.copy_(self._seed_host, non_blocking=True)
 
     def step(self, build_graph):
+        _advance(self._drop_path)
         # the radius graph of this batch: into the tensors of a captured shape when one fits (tried most recent first)
         g = None
         for key, rec in reversed(list(self._graphs.items())):
@@ -256,16 +309,19 @@ class BucketedTrainStep(_BucketedStep):
     molecule: real rows are what the unpadded step computes.  forward_loss(graph, view) -> scalar loss must keep the phantom rows
     out of the loss: reduce per-molecule outputs over `[:view.B]`, per-node outputs with `view.node_mask` -- never with the real
     node or edge count, which a capture would freeze.  The phantom rows then get a zero upstream gradient and add exact zeros to
-    every parameter gradient.  With drop_path_rate > 0 the padded model draws one more random number per call (B + 1 molecules).
+    every parameter gradient.  With drop_path_rate > 0 the phantom molecule is graph B with a draw of its own (droppath.py): the
+    real molecules keep the draws of the unpadded step.
 
     Records are looked up by the step's own bucket key and live side by side; `max_graphs` is honoured by evicting the least
     recently used one (its bucket has to be seen `min_eager` times again).  Each record owns its static inputs (the padded graph
     and target buffers of its bucket), so a batch of another bucket never invalidates a graph.  Eager steps (the first `min_eager`
-    of a bucket) run on the same padded inputs as the replays.  Dropout seed word and AdamW device words as CapturedTrainStep;
-    a reducer is refused likewise."""
+    of a bucket) run on the same padded inputs as the replays.  Dropout seed word, stochastic-depth seed word (`drop_path_seed`)
+    and AdamW device words as CapturedTrainStep; a reducer is refused likewise."""
+
+    _drop_path = None  # (see CapturedTrainStep)
 
     def __init__(self, optimizer, forward_loss, radius, graph_targets=("y",), node_targets=(), min_eager=3, max_graphs=16,
-                 node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000):
+                 node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000, drop_path_seed=None):
         if getattr(optimizer, "_reducer", None) is not None:
             raise ValueError("BucketedTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
         self.opt, self.forward_loss = optimizer, forward_loss
@@ -273,12 +329,14 @@ class BucketedTrainStep(_BucketedStep):
         dev = optimizer.flat_p.device
         self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self._drop_path = _DropPathWord(drop_path_seed, dev)
 
     def _run(self, g, view):
-        self.opt.zero_grad(set_to_none=True)
-        loss = self.forward_loss(g, view)
-        loss.backward()
-        self.opt.step()
+        with _scope(self._drop_path):  # (see CapturedTrainStep._run)
+            self.opt.zero_grad(set_to_none=True)
+            loss = self.forward_loss(g, view)
+            loss.backward()
+            self.opt.step()
         return loss.detach()  # (see CapturedTrainStep._run)
 
     def _draw_seed(self):
@@ -287,7 +345,8 @@ class BucketedTrainStep(_BucketedStep):
 
     def step(self, batch):
         self._check_periodic(batch)
-        self._draw_seed()  # (the device word goes out BEFORE the graph build's host read-back: it overlaps it)
+        self._draw_seed()  # (the device words go out BEFORE the graph build's host read-back: they overlap it)
+        _advance(self._drop_path)
         B, z, plan, build, key = self._plan(batch)
         rec = self._graphs.get(key)
         if rec is not None:

@@ -6,6 +6,7 @@
 // once -- no atomics, deterministic.  The softmax over incoming edges is reduced with wavefront shuffles.
 #include "common.h"
 #include "prof.h"
+#include "rng.h"
 
 namespace {
 
@@ -111,6 +112,37 @@ __global__ __launch_bounds__(256) void segment_scale_kernel(const float* __restr
   float4 v = reinterpret_cast<const float4*>(x)[idx];
   v.x *= f; v.y *= f; v.z *= f; v.w *= f;
   reinterpret_cast<float4*>(out)[idx] = v;
+}
+
+// out[q,c] = f(seg_of[q]) * x[q,c] with the factor of segment_scale_kernel DRAWN here: f = inv_keep where the uniform of
+// (seed0 + *seed_word, tag 32, (call << 32) | graph) (rng.h) is >= drop_p, else 0 -- a pure function of its arguments, so
+// a captured launch whose host advances the word between replays drops other graphs every replay, and its backward
+// (the same launch on dy) redraws the mask of its forward.  One wavefront owns whole rows: the row index is wave-uniform
+// (readfirstlane), so the index load, the two 64-bit hashes and the compare happen once per row on the scalar unit, not
+// once per float4; the lanes stride the row's float4 columns (coalesced 1 KiB per step).  A multiply, not a select: a NaN
+// in a dropped row stays NaN, the bits are those of segment_scale_kernel fed the same factor.
+constexpr unsigned long long DROPPATH_TAG = 32;  // (dens.hip: 0-2, is2rs.hip: 16-18)
+constexpr int DROPPATH_WAVES = 4;
+
+__global__ __launch_bounds__(64 * DROPPATH_WAVES) void segment_droppath_kernel(
+    const float* __restrict__ x, const int* __restrict__ seg_of, float* __restrict__ out, int rows, int D4, float drop_p,
+    float inv_keep, unsigned long long seed0, const unsigned long long* __restrict__ seed_word, unsigned long long call) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)(threadIdx.x & 63);
+  const unsigned long long seed = seed0 + (seed_word ? *seed_word : 0ull);
+  const long stride = (long)gridDim.x * DROPPATH_WAVES;
+  for (long row = (long)blockIdx.x * DROPPATH_WAVES + wave; row < rows; row += stride) {
+    const unsigned long long graph = (unsigned int)seg_of[row];
+    const float u = eqf_rand_uniform(seed, DROPPATH_TAG, (call << 32) | graph);
+    const float f = u >= drop_p ? inv_keep : 0.f;
+    const float4* xr = reinterpret_cast<const float4*>(x) + row * D4;
+    float4* orow = reinterpret_cast<float4*>(out) + row * D4;
+    for (int c = lane; c < D4; c += 64) {
+      float4 v = xr[c];
+      v.x *= f; v.y *= f; v.z *= f; v.w *= f;
+      orow[c] = v;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------- DTP coupling
@@ -633,6 +665,20 @@ int eqf_segment_scale(const float* x, const float* s, const int* seg_of, float* 
   const long total4 = (long)rows * (D / 4);
   hipLaunchKernelGGL(segment_scale_kernel, dim3(eqf_cdiv(total4, 256)), dim3(256), 0, (hipStream_t)stream, x, s, seg_of,
                      out, total4, D / 4);
+  EQF_CHECK_LAUNCH();
+  return 0;
+}
+
+int eqf_segment_droppath(const float* x, const int* seg_of, float* out, int rows, int D, float drop_p, float inv_keep,
+                         unsigned long long seed, const unsigned long long* seed_word, unsigned long long call,
+                         void* stream) {
+  if (!x || !seg_of || !out) return EQF_E_BADARG;
+  if (D % 4) return EQF_E_UNSUPPORTED;
+  if (rows <= 0 || D <= 0) return 0;
+  // one row per wavefront up to 2 048 workgroups (8 per CU), the rows beyond that by the kernel's grid stride
+  const long blocks = eqf_cdiv((long)rows, (long)DROPPATH_WAVES);
+  hipLaunchKernelGGL(segment_droppath_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(64 * DROPPATH_WAVES), 0,
+                     (hipStream_t)stream, x, seg_of, out, rows, D / 4, drop_p, inv_keep, seed, seed_word, call);
   EQF_CHECK_LAUNCH();
   return 0;
 }

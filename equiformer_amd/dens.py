@@ -90,7 +90,7 @@ class DeNSTrainStep:
     Step k corrupts the batch with the seed `step_seed(seed, k)` -- an eager loop that calls
     add_masked_gaussian_noise_to_pos(..., seed=step_seed(seed, k)) sees the same atoms move by the same amounts; torch's
     global generator is not touched -- and hands pos (corrupted), y and the node targets dy, force, noise_vec, noise_mask to
-    a `BucketedTrainStep` (bucket_kwargs: min_eager, max_graphs, node_step, edge_step, max_num_neighbors) whose forward_loss is
+    a `BucketedTrainStep` (bucket_kwargs: min_eager, max_graphs, node_step, edge_step, max_num_neighbors, drop_path_seed) whose forward_loss is
     `model(view, graph=g)` and `loss(E[:view.B], dy_pred, view, row_mask=view.node_mask, num_graphs=view.B)`.  The phantom rows
     of a padded batch have noise_mask 0 and a zero force (nothing encoded) and stay out of the loss through the row mask.
     optimizer: a FlatAdamW without a reducer.  `.last`: the corrupted batch of the latest step; `.bucketed`: the

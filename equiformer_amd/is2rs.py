@@ -105,7 +105,9 @@ class IS2RSTrainStep:
     generator is not touched, the caller's `pos` is not written.  With `total_steps` the loss's auxiliary device word is set to
     `auxiliary_task_weight(w0, k, total_steps)` before the step, w0 = the constructor's `auxiliary_task_weight` (default: the
     weight `loss` holds at construction).  The perturbed pos, y and the node targets tags, pos_relaxed then go to a periodic
-    `BucketedTrainStep` (bucket_kwargs: min_eager, max_graphs, node_step, edge_step) whose forward_loss is
+    `BucketedTrainStep` (bucket_kwargs: min_eager, max_graphs, node_step, edge_step, drop_path_seed -- default `seed`: step k of
+    a model with drop_path_rate > 0 drops what an eager step under `droppath.device_draws(step_seed(seed, k))` drops) whose
+    forward_loss is
     `model(view, graph=g, offsets=view.offsets)` and `loss(E[:view.B], vectors, view, row_mask=view.node_mask,
     num_graphs=view.B)`.  The phantom rows of a padded batch have tag 0 and stay out of the loss through the row mask as well.
     model: an OC20 model with use_auxiliary_task=True (either head); optimizer: a FlatAdamW without a reducer.  `.last`: the
@@ -127,6 +129,7 @@ class IS2RSTrainStep:
         self.w0 = auxiliary_task_weight
         self.steps = 0
         self.last = None
+        bucket_kwargs.setdefault("drop_path_seed", self.seed)  # (its own stream of the seed: the kernels separate them by tag)
         self.bucketed = BucketedTrainStep(optimizer, self._forward_loss, radius, graph_targets=("y",),
                                           node_targets=self.NODE_TARGETS, max_num_neighbors=max_num_neighbors, **bucket_kwargs)
 

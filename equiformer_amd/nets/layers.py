@@ -21,7 +21,7 @@ import os
 import torch
 from torch import nn
 
-from .. import ops, so3
+from .. import droppath, ops, so3
 from ..irreps import Irrep, Irreps
 from ..layout import DtpTable, RowLayout
 
@@ -813,7 +813,9 @@ class FeedForwardNetwork(nn.Module):
 class GraphDropPath(nn.Module):
     """Per-graph stochastic depth [ref: nets/drop.py:45-61]: in training every graph of the batch keeps the branch with
     probability 1 - drop_prob (scaled by 1/keep), decided by one draw per graph from torch's CPU generator (fp64, the
-    stream the fp64 oracle consumes under the same seed); the row scaling itself is eqf_segment_scale."""
+    stream the fp64 oracle consumes under the same seed); the row scaling itself is eqf_segment_scale.  Inside a
+    `droppath.device_draws` scope the draw happens in the kernel instead (eqf_segment_droppath: a function of the scope's
+    seed, its call counter and the graph's index), which is what a captured step needs for a fresh mask per replay."""
 
     def __init__(self, drop_prob=None):
         super().__init__()
@@ -822,6 +824,9 @@ class GraphDropPath(nn.Module):
     def forward(self, x, graph):
         if not self.drop_prob or not self.training:
             return x
+        draws = droppath.active()
+        if draws is not None:
+            return droppath.segment_droppath(x, graph.batch, self.drop_prob, draws.seed, draws.next_call(), draws.word)
         keep = 1.0 - self.drop_prob
         r = torch.rand((graph.num_graphs, 1), dtype=torch.float64)
         s = ((keep + r).floor_() / keep).to(torch.float32).view(-1)

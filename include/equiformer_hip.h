@@ -536,6 +536,18 @@ int eqf_edgedeg_scatter_bwd(const float* dnode, const float* coupling, const int
 int eqf_segment_scale(const float* x, const float* s, const int* seg_of, float* out, int rows, int D,
                       void* stream);
 
+/* The same row scaling with the factor DRAWN on the device: out[q,:] = f(seg_of[q]) * x[q,:],
+ *   f(g) = u(g) >= drop_p ? inv_keep : 0,   u(g) = the uniform of csrc/rng.h for
+ *   seed + (seed_word ? *seed_word : 0) (mod 2^64), stream tag 32, index (call << 32) | g.
+ * inv_keep: 1 / (1 - drop_p), rounded to fp32 by the caller.  seed_word: a device word (may be NULL) that the host
+ * advances between the replays of a captured step; call: which stochastic-depth call of the step this is.  A pure
+ * function of its arguments and linear in x: its backward and second-order term are the same call on dy with the same
+ * (seed, seed_word, call).  A multiply, never a select: bit-equal to eqf_segment_scale fed the same factors.
+ * D % 4 == 0 (else EQF_E_UNSUPPORTED before any launch); rows == 0 launches nothing. */
+int eqf_segment_droppath(const float* x, const int* seg_of, float* out, int rows, int D, float drop_p, float inv_keep,
+                         unsigned long long seed, const unsigned long long* seed_word, unsigned long long call,
+                         void* stream);
+
 /* Depth-wise tensor product, un-fused form (kept as the building block for shapes the fused GEMM
  * does not cover and as its on-device cross-check): out[e, :] per eqf_dtp_paths.  w may be NULL.
  * [ref: DepthwiseTensorProduct + o3.TensorProduct('uvu'), nets/graph_attention_transformer.py:157-183] */

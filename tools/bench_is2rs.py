@@ -2,9 +2,10 @@
 """The IS2RE + IS2RS train step three ways, one MI355X, one process, one build:
 
     python tools/bench_is2rs.py [--batches 48] [--regions 3] [--out profiles/is2rs_step.json]
+    python tools/bench_is2rs.py --drop-path-rate 0.05 --out profiles/is2rs_step_droppath.json
 
-The `l1_256_nonlinear_aux` model (6 blocks, feature 512x0e+256x1e, IS2RS head; drop_path_rate 0: the per-graph stochastic-depth
-draw is made on the host and would be frozen into a graph), 16 slab structures of 60-96 atoms per batch
+The `l1_256_nonlinear_aux` model (6 blocks, feature 512x0e+256x1e, IS2RS head; drop_path_rate 0 unless --drop-path-rate says
+otherwise, see the end), 16 slab structures of 60-96 atoms per batch
 (synthetic.oc20_like_varying_batches, as tools/bench_varying_oc20.py), relaxed positions = pos + 0.2 A Gaussian on the free
 atoms, r = 5, max_neighbors = 500, the auxiliary weight decaying from 15.  Three loops over the same batches:
   (A) `aten`:     the step as the reference writes it (base_trainer_v2.py:81-126, energy_trainer_v2.py:413-442): ATen
@@ -16,6 +17,14 @@ Every step is timed on its own (device-synchronised wall clock); one region = on
 region by region; untimed passes first (the captured leg: min_eager + 1 of them, so that every bucket has its graph).  Median,
 p10 and p90 of the step time and structures/s (real structures over the median step) per leg.  The launches of the perturbation
 and of the loss + its backward ALONE (stand-in predictions, no model) are counted with the torch profiler for (A) and (B).
+
+--drop-path-rate P > 0 (the shipped configuration: 0.05) times per-graph stochastic depth instead, four legs over the same
+batches in one run, one model:
+  `captured`:      IS2RSTrainStep, the keep mask drawn in the kernel from the step's device word (equiformer_amd/droppath.py);
+  `eager_device`:  (B) under droppath.device_draws(step_seed(seed, k)): the same draws, launched from the host;
+  `eager_host`:    (B) with the mask drawn from torch's CPU generator and uploaded, call by call -- the only way to train this
+                   configuration without the device draw;
+  `captured_p0`:   IS2RSTrainStep with the rate set to 0 while its graphs are captured: what stochastic depth costs a replay.
 Prints one JSON line."""
 import argparse
 import json
@@ -78,6 +87,91 @@ def count_launches(fn, iters=4):
     return {"kernels": (len(evs) - copies) / iters, "copies_and_fills": copies / iters}
 
 
+def summary(v, B):
+    s = sorted(v)
+    q = lambda p: s[min(len(s) - 1, int(round(p * (len(s) - 1))))]  # noqa: E731
+    return {"median_ms": q(0.5), "p10_ms": q(0.1), "p90_ms": q(0.9), "structures_per_s": B / (q(0.5) * 1e-3), "steps": len(s)}
+
+
+def row_scaling_alone(rate, rows=1248, D=768, graphs=16, launches=200, repeats=7):
+    """The two row scalings alone on [rows, D] (16 structures of 78 atoms, the feature width 512x0e+256x1e): eqf_segment_droppath
+    (factor drawn in the kernel) against eqf_segment_scale (factor read from a table).  Device events around `launches`
+    back-to-back launches, the two alternating, median over `repeats` blocks: microseconds per launch INCLUDING the rate at which
+    the host launches -- not a kernel time."""
+    from equiformer_amd import droppath, ops
+    dev = torch.device("cuda:0")
+    x = torch.randn(rows, D, device=dev)
+    seg = torch.repeat_interleave(torch.arange(graphs, dtype=torch.int32), rows // graphs).to(dev)
+    f = droppath.keep_factors(0, 0, graphs, rate).to(dev)
+    fns = {"segment_droppath": lambda: droppath.segment_droppath(x, seg, rate, 0, 0),
+           "segment_scale": lambda: ops.segment_scale(x, f, seg)}
+    assert torch.equal(fns["segment_droppath"](), fns["segment_scale"]())
+    us = {k: [] for k in fns}
+    for _ in range(repeats + 1):  # (the first block of each: untimed warm-up)
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(launches):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3 / launches)
+    med = {k: sorted(v[1:])[len(v[1:]) // 2] for k, v in us.items()}
+    return {"rows": rows, "D": D, "graphs": graphs, "us_per_launch": med, "blocks": {k: v[1:] for k, v in us.items()},
+            "bytes_moved": 8 * rows * D,
+            "how": "device events around %d back-to-back launches through the Python operator, alternating, median of %d blocks; "
+                   "includes the host's launch rate" % (launches, repeats)}
+
+
+def stochastic_depth_legs(args, rate, batches, B, lib, ts, ts0, L, legs):
+    """--drop-path-rate > 0: the four legs of the module docstring, timed as the default run times its three"""
+    def one_pass(step):
+        out = []
+        for d in batches:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step(d)
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return out
+
+    for name, step in legs:  # untimed: one pass of the eager legs, min_eager + 1 of the captured ones (every bucket has its graph)
+        for _ in range(ts.bucketed.min_eager + 1 if name.startswith("captured") else 1):
+            one_pass(step)
+    warm = {n: dict(eager_steps=t.eager_steps, captures=t.captures, replays=t.replays) for n, t in (("captured", ts), ("captured_p0", ts0))}
+    ms = {name: [] for name, _ in legs}
+    for _ in range(args.regions):
+        for name, step in legs:
+            ms[name] += one_pass(step)
+    res = {name: summary(v, B) for name, v in ms.items()}
+    out = {
+        "what": "IS2RE + IS2RS train step with per-graph stochastic depth, %s (drop_path_rate %g), %d different batches of %d slab "
+                "structures (%d-%d atoms), r=%.1f, max_neighbors=%d, split mode, one process, one model; device-synchronised wall "
+                "time per step, one region = one pass over all batches, legs alternating"
+                % (MODEL, rate, len(batches), B, args.atoms_min, args.atoms_max, RADIUS, MAX_NEIGHBORS),
+        "build": lib.built_hash(), "regions": args.regions, "drop_path_rate": rate,
+    }
+    out.update(res)
+    out["captured_range_ms"] = res["captured"]["p90_ms"] - res["captured"]["p10_ms"]
+    out["eager_host_range_ms"] = res["eager_host"]["p90_ms"] - res["eager_host"]["p10_ms"]
+    out["captured_over_eager_host"] = res["eager_host"]["median_ms"] / res["captured"]["median_ms"]
+    out["captured_over_eager_device"] = res["eager_device"]["median_ms"] / res["captured"]["median_ms"]
+    out["cost_over_captured_p0_ms"] = res["captured"]["median_ms"] - res["captured_p0"]["median_ms"]
+    out["row_scaling_alone"] = row_scaling_alone(rate)
+    out["warmup"] = warm
+    out["captured_timed"] = {n: dict(eager_steps=t.eager_steps - warm[n]["eager_steps"], captures=t.captures - warm[n]["captures"],
+                                     replays=t.replays - warm[n]["replays"], live_graphs=len(t.bucketed.live_graphs()))
+                             for n, t in (("captured", ts), ("captured_p0", ts0))}
+    out["last_stats"] = dict(zip(("loss_e", "loss_aux", "n_free", "energy_mae", "energy_mse", "energy_within_threshold", "pos_mae"),
+                                 L.stats.cpu().tolist()))
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=48)
@@ -88,11 +182,13 @@ def main():
     ap.add_argument("--node-step", type=int, default=64)
     ap.add_argument("--edge-step", type=int, default=2048)
     ap.add_argument("--max-graphs", type=int, default=16)
+    ap.add_argument("--drop-path-rate", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "is2rs_step.json"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_is2rs.py needs an MI355X"
-    from equiformer_amd import lib, nets, ops
-    from equiformer_amd.is2rs import IS2RSLoss, IS2RSTrainStep, auxiliary_task_weight, interpolate_init_relaxed_pos
+    from equiformer_amd import droppath, lib, nets, ops
+    from equiformer_amd.is2rs import IS2RSLoss, IS2RSTrainStep, auxiliary_task_weight, interpolate_init_relaxed_pos, step_seed
+    from equiformer_amd.nets.layers import GraphDropPath
     from equiformer_amd.optim import FlatAdamW, add_weight_decay
     from equiformer_amd.synthetic import oc20_like_varying_batches
     lib.load()
@@ -100,7 +196,13 @@ def main():
     torch.manual_seed(0)
     B = args.structures
     assert ops.get_matrix_mode() == "split"
-    model = nets.model_entrypoint(MODEL)(drop_path_rate=0.0).to(dev).train()
+    rate = float(args.drop_path_rate)
+    model = nets.model_entrypoint(MODEL)(drop_path_rate=rate).to(dev).train()
+    drop_modules = [m for m in model.modules() if isinstance(m, GraphDropPath)]
+
+    def set_rate(p):  # (read when a step is launched from the host: an eager step or a capture, never a replay)
+        for m in drop_modules:
+            m.drop_prob = p
     opt = FlatAdamW(add_weight_decay(model, 1e-3, model.no_weight_decay()), lr=2e-4)
     gen = torch.Generator().manual_seed(7)
     batches = []
@@ -135,6 +237,26 @@ def main():
         opt.step()
 
     legs = [("aten", step_aten), ("fused", step_fused), ("captured", ts.step)]
+    if rate > 0.0:
+        ts0 = IS2RSTrainStep(model, opt, L, RADIUS, MAX_NEIGHBORS, interpolate=True, seed=0, total_steps=total_steps,
+                             auxiliary_task_weight=W0, node_step=args.node_step, edge_step=args.edge_step,
+                             max_graphs=args.max_graphs)
+        counter["device"] = 0
+
+        def step_device(d):
+            with droppath.device_draws(step_seed(0, counter["device"])):
+                counter["device"] += 1
+                step_fused(d)
+
+        def step_p0(d):
+            set_rate(0.0)
+            try:
+                ts0.step(d)
+            finally:
+                set_rate(rate)
+        return stochastic_depth_legs(args, rate, batches, B, lib, ts, ts0, L,
+                                     [("captured", ts.step), ("eager_device", step_device), ("eager_host", step_fused),
+                                      ("captured_p0", step_p0)])
 
     def one_pass(step):
         out = []
@@ -182,12 +304,7 @@ def main():
         for name, step in legs:  # alternating: a drift of the box's clocks reaches every leg alike
             ms[name] += one_pass(step)
 
-    def summary(v):
-        s = sorted(v)
-        q = lambda p: s[min(len(s) - 1, int(round(p * (len(s) - 1))))]  # noqa: E731
-        return {"median_ms": q(0.5), "p10_ms": q(0.1), "p90_ms": q(0.9), "structures_per_s": B / (q(0.5) * 1e-3), "steps": len(s)}
-
-    res = {name: summary(v) for name, v in ms.items()}
+    res = {name: summary(v, B) for name, v in ms.items()}
     bk = ts.bucketed
     out = {
         "what": "IS2RE + IS2RS train step, %s (drop_path_rate 0), %d different batches of %d slab structures (%d-%d atoms), r=%.1f, "
