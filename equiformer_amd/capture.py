@@ -30,10 +30,12 @@ periodic structures (`model(data, graph=g, offsets=g.offsets)`) is captured exac
 (tests/test_gpu_periodic_capture.py, tools/bench_varying_oc20.py).
 
 Limits: one process / one GPU (a data-parallel reducer's collectives stay eager: `CapturedTrainStep` refuses a reducer),
-attention dropout together with a create_graph backward (no model of the reference combines them), graphs built on the GPU from
-positions only (an edge list that comes from outside -- OC20 with otf_graph=False -- is sorted by EdgeGraph.from_edges with a
-device sort on the host side of the step: eager), inputs other than the graph at fixed addresses (`forward_loss` reads the same
-tensors every step; copy a new batch into them)."""
+attention dropout together with a create_graph backward (no model of the reference combines them), graphs built by the enqueue-only
+builders only -- from positions (`from_radius`, `from_radius_pbc`) or from the periodic edge list an OC20 batch carries
+(`from_edges_pbc`: otf_graph=False; the step classes take it with `edges="batch"`); an arbitrary edge list without the
+`neighbors` / `cell_offsets` contract still goes through EdgeGraph.from_edges and its device sort: eager --, structures of at most
+`graph.CSR_MAX_NODES` nodes, inputs other than the graph at fixed addresses (`forward_loss` reads the same tensors every step;
+copy a new batch into them)."""
 import contextlib
 
 import torch
@@ -191,6 +193,22 @@ def bucket_corner(key, node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP)
     return key[1] - min_phantom_nodes(int(edge_step) - 1), key[2]
 
 
+GIVEN_EDGE_FIELDS = ("edge_index", "cell_offsets", "neighbors", "cell")
+
+
+def given_edge_fields(batch):
+    """The fields a batch must carry for `edges="batch"`, the ocpmodels contract of otf_graph=False: `edge_index` [2, E]
+    (neighbour, centre), `cell_offsets` [E, 3] (integer images), `neighbors` [B] (edges per structure), `cell` [B, 3, 3].  Raises
+    ValueError naming every missing one (a non-periodic batch has no `cell`); returns the names.  batch: a mapping or an object
+    with attributes.  A pure host function."""
+    has = (lambda n: n in batch and batch[n] is not None) if hasattr(batch, "keys") else (lambda n: getattr(batch, n, None) is not None)
+    missing = [n for n in GIVEN_EDGE_FIELDS if not has(n)]
+    if missing:
+        raise ValueError("edges=\"batch\" needs the batch's own periodic edge list: %s missing (needed: %s)"
+                         % (", ".join(missing), ", ".join(GIVEN_EDGE_FIELDS)))
+    return GIVEN_EDGE_FIELDS
+
+
 class PaddedBatch:
     """What `forward_loss(graph, view)` of a BucketedTrainStep reads: the padded inputs `pos` [N_cap, 3], `z` [N_cap], `batch`
     [N_cap], the masks `node_mask` [N_cap] / `graph_mask` [B + 1] (1.0 real, 0.0 phantom), `B` (real molecules: constant per
@@ -205,8 +223,13 @@ class _BucketedStep:
     counters, the padded view of a bucket's graph, its target buffers, and the first half of a step (the plan of the batch's
     radius graph -- the one host read-back -- and its bucket key)."""
 
-    def _init_buckets(self, radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors):
+    def _init_buckets(self, radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors,
+                      edges="search"):
         import collections
+        if edges not in ("search", "batch"):
+            raise ValueError("edges must be \"search\" (neighbours found on the GPU) or \"batch\" (the batch's own edge list), got %r"
+                             % (edges,))
+        self.edges = edges  # ("batch": radius and max_num_neighbors do not enter the graph)
         self.radius, self.max_num_neighbors = float(radius), int(max_num_neighbors)
         self.graph_targets, self.node_targets = tuple(graph_targets), tuple(node_targets)
         self.min_eager, self.max_graphs = int(min_eager), max(1, int(max_graphs))
@@ -250,7 +273,11 @@ class _BucketedStep:
         b = batch["batch"]
         B = int(batch["num_graphs"]) if "num_graphs" in batch else int(b[-1].item()) + 1
         z = batch["z"] if "z" in batch else batch.get("atomic_numbers")
-        if self._periodic:
+        if self.edges == "batch":
+            plan = EdgeGraph.edges_pbc_plan(batch["pos"], batch["cell"], b, batch["edge_index"], batch["cell_offsets"],
+                                            batch["neighbors"], B)
+            build = EdgeGraph.from_edges_pbc_plan
+        elif self._periodic:
             plan = EdgeGraph.radius_pbc_plan(batch["pos"], batch["cell"], b, self.radius, self.max_num_neighbors, B)
             build = EdgeGraph.from_radius_pbc_plan
         else:
@@ -264,6 +291,8 @@ class _BucketedStep:
         return B, z, plan, build, key
 
     def _check_periodic(self, batch):
+        if self.edges == "batch":
+            given_edge_fields(batch)  # (a non-periodic batch lacks `cell`: refused here)
         periodic = "cell" in batch
         if self._periodic is None:
             self._periodic = periodic
@@ -301,7 +330,9 @@ class BucketedTrainStep(_BucketedStep):
     A batch with `cell` [B, 3, 3] is periodic: the graph is the periodic one (EdgeGraph.radius_pbc_plan / from_radius_pbc_plan,
     `radius` and `max_num_neighbors` of the constructor), `atomic_numbers` is accepted for `z`, and per-node INPUTS such as the
     OC20 `tags` travel through `node_targets` (a zero row is a valid tag).  One instance serves periodic or non-periodic
-    batches, not both.
+    batches, not both.  edges="batch": the periodic batch brings its own edge list (`given_edge_fields`: edge_index, cell_offsets,
+    neighbors, cell -- what an OC20 LMDB delivers, the reference's otf_graph=False); the graph is EdgeGraph.edges_pbc_plan /
+    from_edges_pbc_plan, no neighbour search runs, and `radius` / `max_num_neighbors` do not enter it.
 
     Every batch is padded to the capacity of its bucket (`bucket_of`) with one phantom molecule (EdgeGraph.from_radius(...,
     capacity=)), the unchanged kernels run on the padded shape, and one HIP graph per BUCKET replays forward + loss + backward +
@@ -321,11 +352,13 @@ class BucketedTrainStep(_BucketedStep):
     _drop_path = None  # (see CapturedTrainStep)
 
     def __init__(self, optimizer, forward_loss, radius, graph_targets=("y",), node_targets=(), min_eager=3, max_graphs=16,
-                 node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000, drop_path_seed=None):
+                 node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000, drop_path_seed=None,
+                 edges="search"):
         if getattr(optimizer, "_reducer", None) is not None:
             raise ValueError("BucketedTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
         self.opt, self.forward_loss = optimizer, forward_loss
-        self._init_buckets(radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors)
+        self._init_buckets(radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors,
+                           edges)
         dev = optimizer.flat_p.device
         self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()

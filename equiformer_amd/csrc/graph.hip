@@ -314,6 +314,118 @@ __global__ __launch_bounds__(256) void csr_by_source_multi_kernel(const int* __r
   }
 }
 
+// ---------------------------------------------------------------------------------------------- given periodic edge list
+// The edge list an ocpmodels batch carries (edge_index = (neighbour, centre), integer cell_offsets, `neighbors` edges per
+// structure) turned into the dst-sorted graph [ref: nets/graph_attention_transformer_oc20.py:280-293; get_pbc_distances
+// restated in oracle/pbc.py:get_pbc_distances]: count = offsets, the zero-length test and the in-degrees; fill = a counting
+// sort on the destination that is stable in input order.  Indices and images are read as the loader stores them (int64 or
+// int32) and checked against the structure's node range before anything is indexed with them.
+constexpr int EDGES_PASS = 256;       // input edges a structure's workgroup places per pass (graph.py EDGES_PASS)
+constexpr int EDGES_ST_NODE = 1;      // status bit: an edge names a node outside its structure
+constexpr int EDGES_ST_RANGE = 2;     // status bit: an input edge belongs to no structure (`neighbors` does not cover it)
+
+__device__ __forceinline__ long long edges_load(const void* __restrict__ p, long k, int is64) {
+  return is64 ? ((const long long*)p)[k] : (long long)((const int*)p)[k];
+}
+
+__global__ __launch_bounds__(256) void edges_pbc_count_kernel(const float* __restrict__ pos, const float* __restrict__ cell,
+                                                              const int* __restrict__ mol_ptr, const int* __restrict__ nbr_ptr,
+                                                              int n_mol, int n_nodes, const void* __restrict__ edge_index,
+                                                              int index64, const void* __restrict__ cell_offsets, int offsets64,
+                                                              int e_in, unsigned char* __restrict__ keep, float* __restrict__ off,
+                                                              int* __restrict__ deg, int* __restrict__ status) {
+  // offset = (n1 a1 + n2 a2) + n3 a3 and vec = (pos_j - pos_i) + offset as separately rounded fp32 operations: an FMA that folds
+  // a product into the sum that follows changes which edges come out as exactly zero (csrc/is2rs.hip on the pragma)
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= e_in) return;
+  keep[e] = 0;
+  off[3 * (long)e] = 0.f, off[3 * (long)e + 1] = 0.f, off[3 * (long)e + 2] = 0.f;
+  int lo = 0, hi = n_mol;  // the structure of e: the first b with nbr_ptr[b + 1] > e
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (nbr_ptr[mid + 1] <= e) lo = mid + 1;
+    else hi = mid;
+  }
+  const int b = lo;
+  if (b >= n_mol || nbr_ptr[b] > e) {
+    atomicOr(status, EDGES_ST_RANGE);
+    return;
+  }
+  const long long j = edges_load(edge_index, e, index64), i = edges_load(edge_index, (long)e_in + e, index64);
+  const long long n0 = max(mol_ptr[b], 0), n1 = min(mol_ptr[b + 1], n_nodes);
+  if (j < n0 || j >= n1 || i < n0 || i >= n1) {  // (never dereferenced)
+    atomicOr(status, EDGES_ST_NODE);
+    return;
+  }
+  const float* c = cell + 9 * (long)b;
+  const float u = (float)edges_load(cell_offsets, 3 * (long)e, offsets64), v = (float)edges_load(cell_offsets, 3 * (long)e + 1, offsets64),
+              w = (float)edges_load(cell_offsets, 3 * (long)e + 2, offsets64);
+  bool kept = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float o = (u * c[k] + v * c[3 + k]) + w * c[6 + k];
+    const float d = (pos[3 * j + k] - pos[3 * i + k]) + o;
+    off[3 * (long)e + k] = o;
+    kept = kept || (d != 0.f);
+  }
+  if (kept) {
+    keep[e] = 1;
+    atomicAdd(&deg[i], 1);  // (integer: the count does not depend on the order)
+  }
+}
+
+// One workgroup per structure: cur[node] = the next free slot of the node's row (LDS), the structure's input range walked in
+// passes of EDGES_PASS edges.  Inside a pass the slot of a kept edge is cur[dst] + (kept edges before it in the pass with the same
+// destination); the cursors advance only after the whole pass was placed, so no thread reads a cursor another one is bumping
+// (the pattern of csr_by_source_multi_kernel, and its limit: lds_nodes cursors, larger structures are skipped -- the entry point
+// has refused them).  Every store is bounds-checked against n_kept.
+__global__ __launch_bounds__(EDGES_PASS) void edges_pbc_fill_kernel(const int* __restrict__ mol_ptr, const int* __restrict__ nbr_ptr,
+                                                                    int lds_nodes, const void* __restrict__ edge_index, int index64,
+                                                                    const void* __restrict__ cell_offsets_in, int offsets64, int e_in,
+                                                                    const unsigned char* __restrict__ keep,
+                                                                    const float* __restrict__ off, const int* __restrict__ row_ptr,
+                                                                    int n_kept, int* __restrict__ src, int* __restrict__ dst,
+                                                                    int* __restrict__ cell_offsets, float* __restrict__ offsets,
+                                                                    int* __restrict__ order) {
+  extern __shared__ int cur[];  // [nm]
+  __shared__ int pass_dst[EDGES_PASS];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int n0 = mol_ptr[b], n1 = mol_ptr[b + 1], nm = n1 - n0;
+  if (nm <= 0 || nm > lds_nodes) return;
+  const int a0 = min(max(nbr_ptr[b], 0), e_in), a1 = min(max(nbr_ptr[b + 1], a0), e_in);
+  for (int i = t; i < nm; i += EDGES_PASS) cur[i] = row_ptr[n0 + i];
+  __syncthreads();
+  for (int base = a0; base < a1; base += EDGES_PASS) {
+    const int e = base + t;
+    int d = -1;
+    long long j = 0;
+    if (e < a1 && keep[e]) {
+      j = edges_load(edge_index, e, index64);
+      const long long i = edges_load(edge_index, (long)e_in + e, index64);
+      if (i >= n0 && i < n1 && j >= n0 && j < n1) d = (int)(i - n0);
+    }
+    pass_dst[t] = d;
+    __syncthreads();
+    if (d >= 0) {
+      int k = 0;
+      for (int q = 0; q < t; ++q) k += (pass_dst[q] == d) ? 1 : 0;
+      const int slot = cur[d] + k;
+      if (slot >= 0 && slot < n_kept) {
+        src[slot] = (int)j, dst[slot] = n0 + d, order[slot] = e;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          cell_offsets[3 * (long)slot + c] = (int)edges_load(cell_offsets_in, 3 * (long)e + c, offsets64);
+          offsets[3 * (long)slot + c] = off[3 * (long)e + c];
+        }
+      }
+    }
+    __syncthreads();
+    if (d >= 0) atomicAdd(&cur[d], 1);
+    __syncthreads();
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- padding to a capacity
 // Tail of a batch padded to (n_cap, e_cap) with ONE phantom molecule: P = n_cap - n nodes, Q = e_cap - e edges among them.
 // Phantom node i (0 <= i < P) is the destination of d_i = Q / P + (i < Q % P) edges (in-degrees differ by at most one)
@@ -694,6 +806,49 @@ int eqf_csr_by_source_multi(const int* src, const int* row_ptr, const int* mol_p
   const int lds_nodes = max_mol_nodes > 0 ? max_mol_nodes : 1;
   hipLaunchKernelGGL(csr_by_source_multi_kernel, dim3(n_mol), dim3(256), sizeof(int) * (size_t)lds_nodes, (hipStream_t)stream,
                      src, row_ptr, mol_ptr, n_mol, lds_nodes, src_perm, src_ptr);
+  EQF_CHECK_LAUNCH();
+  return 0;
+}
+
+int eqf_edges_pbc_count(const float* pos, const float* cell, const int* mol_ptr, const int* nbr_ptr, int n_mol, int n_nodes,
+                        const void* edge_index, int index_is64, const void* cell_offsets, int offsets_is64, int n_edges,
+                        unsigned char* keep, float* off, int* deg, int* status, void* stream) {
+  if (!mol_ptr || !nbr_ptr || !status || n_mol < 0 || n_nodes < 0 || n_edges < 0) return EQF_E_BADARG;
+  if (n_nodes > 0 && (!pos || !deg)) return EQF_E_BADARG;
+  if (n_edges > 0 && (!pos || !cell || !edge_index || !cell_offsets || !keep || !off)) return EQF_E_BADARG;
+  hipError_t err = hipMemsetAsync(status, 0, sizeof(int), (hipStream_t)stream);
+  if (err == hipSuccess && n_nodes > 0) err = hipMemsetAsync(deg, 0, sizeof(int) * (size_t)n_nodes, (hipStream_t)stream);
+  if (err != hipSuccess) return (int)err;
+  if (n_edges == 0) return 0;
+  hipLaunchKernelGGL(edges_pbc_count_kernel, dim3(eqf_cdiv(n_edges, 256)), dim3(256), 0, (hipStream_t)stream, pos, cell,
+                     mol_ptr, nbr_ptr, n_mol, n_nodes, edge_index, index_is64, cell_offsets, offsets_is64, n_edges, keep, off,
+                     deg, status);
+  EQF_CHECK_LAUNCH();
+  return 0;
+}
+
+int eqf_edges_pbc_fill(const int* mol_ptr, const int* nbr_ptr, int n_mol, int max_mol_nodes, const void* edge_index,
+                       int index_is64, const void* cell_offsets_in, int offsets_is64, int n_edges, const unsigned char* keep,
+                       const float* off, const int* row_ptr, int n_kept, int* src, int* dst, int* cell_offsets, float* offsets,
+                       int* order, void* stream) {
+  if (!mol_ptr || !nbr_ptr || !row_ptr || n_mol < 0 || n_edges < 0 || n_kept < 0 || n_kept > n_edges) return EQF_E_BADARG;
+  if (n_edges > 0 && (!edge_index || !cell_offsets_in || !keep || !off)) return EQF_E_BADARG;
+  if (n_kept > 0 && (!src || !dst || !cell_offsets || !offsets || !order)) return EQF_E_BADARG;
+  if (max_mol_nodes > CSR_MAX_NODES) return EQF_E_UNSUPPORTED;
+  if (n_mol == 0 || n_kept == 0) return 0;
+  static bool attr_done[64] = {};  // per device (function attribute)
+  int dev_id = 0;
+  (void)hipGetDevice(&dev_id);
+  bool& attr = attr_done[dev_id & 63];
+  if (!attr) {
+    hipFuncSetAttribute((const void*)edges_pbc_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        CSR_MAX_NODES * (int)sizeof(int));
+    attr = true;
+  }
+  const int lds_nodes = max_mol_nodes > 0 ? max_mol_nodes : 1;
+  hipLaunchKernelGGL(edges_pbc_fill_kernel, dim3(n_mol), dim3(EDGES_PASS), sizeof(int) * (size_t)lds_nodes, (hipStream_t)stream,
+                     mol_ptr, nbr_ptr, lds_nodes, edge_index, index_is64, cell_offsets_in, offsets_is64, n_edges, keep, off,
+                     row_ptr, n_kept, src, dst, cell_offsets, offsets, order);
   EQF_CHECK_LAUNCH();
   return 0;
 }

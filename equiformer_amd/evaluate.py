@@ -14,7 +14,9 @@ batch.  Here:
     read the parameters at their addresses: a replay sees the weights as they are then (an optimizer step or an EMA copy made in
     place between two passes is seen; parameters REPLACED by new tensors are not).
   * `evaluate_qm9`, `evaluate_md17`, `evaluate_oc20` are the three loops behind that interface.
-OC20 batches with a precomputed edge list (otf_graph=False) and data-parallel evaluation stay eager."""
+OC20 batches with a precomputed edge list (otf_graph=False) are served with `edges="batch"` (BucketedEvalStep, oc20_eval_step and
+evaluate_oc20 through their bucket_kwargs): the graph comes from EdgeGraph.edges_pbc_plan / from_edges_pbc_plan, no neighbour
+search runs.  Data-parallel evaluation stays eager."""
 import collections
 import functools
 
@@ -143,14 +145,16 @@ class BucketedEvalStep(_BucketedStep):
     are not what an evaluation captures."""
 
     def __init__(self, predict, radius, meter=None, graph_targets=("y",), node_targets=(), min_eager=3, max_graphs=16,
-                 node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000, device=None, model=None):
+                 node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000, device=None, model=None,
+                 edges="search"):
         self.predict, self.meter = predict, meter
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
             raise ops.HipOnlyError("the evaluation step runs on MI355X only (got device %s); there is no CPU fallback" % self.device)
         mods = [] if model is None else ([model] if isinstance(model, torch.nn.Module) else list(model))
         self._models = mods + [m for m in _modules_of(predict) if all(m is not k for k in mods)]
-        self._init_buckets(radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors)
+        self._init_buckets(radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors,
+                           edges)
 
     def _check_eval(self):
         for m in self._models:
@@ -269,8 +273,9 @@ def evaluate_md17(model, loader, radius, step=None, **bucket_kwargs):
 
 
 def oc20_eval_step(model, radius, task_mean=0.0, task_std=1.0, threshold=0.02, node_targets=("tags",), **bucket_kwargs):
-    """The BucketedEvalStep of `evaluate_oc20`: periodic batches (`cell`), graph built on the fly.  task_mean / task_std: the
-    trainer's target normalizer (0, 1 without normalize_labels)."""
+    """The BucketedEvalStep of `evaluate_oc20`: periodic batches (`cell`), graph built on the fly -- or, with edges="batch" among
+    bucket_kwargs, from the batch's own edge_index / cell_offsets / neighbors.  task_mean / task_std: the trainer's target
+    normalizer (0, 1 without normalize_labels)."""
     dev = next(model.parameters()).device
     meter = Meter(task_mean, task_std, threshold, device=dev)
 

@@ -34,6 +34,7 @@ def _stream():
 
 
 CSR_MAX_NODES = 16384  # nodes per molecule the by-source kernel keeps cursors for (csrc/graph.hip)
+EDGES_PASS = 256       # input edges per pass of eqf_edges_pbc_fill (csrc/graph.hip): a row's edges may straddle a pass boundary
 
 
 class GraphDoesNotFit(ValueError):
@@ -65,6 +66,14 @@ class PbcPlan:
     scan of the nearest-k selection and the candidate total (the size of its scratch)."""
     __slots__ = ("pos", "cell", "b32", "N", "E", "C", "num_graphs", "mol_ptr", "row_ptr", "cand_ptr", "max_mol_nodes", "r",
                  "max_num_neighbors")
+
+
+class EdgesPbcPlan:
+    """The first half of a build from a GIVEN periodic edge list (`EdgeGraph.edges_pbc_plan`): the input as the loader delivers
+    it, the scan of `neighbors`, the kept mask and fp32 Cartesian offset per input edge, the kept in-degrees' scan and the host
+    read-back (E = kept edges, E_in = input edges)."""
+    __slots__ = ("pos", "cell", "b32", "N", "E", "E_in", "num_graphs", "mol_ptr", "nbr_ptr", "row_ptr", "max_mol_nodes",
+                 "edge_index", "cell_offsets", "index64", "offsets64", "keep", "off")
 
 
 class EdgeGraph:
@@ -382,6 +391,162 @@ class EdgeGraph:
         call("eqf_csr_by_source_multi", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
              _P(g.src_perm), _P(g.src_ptr), st)
         return g
+
+    # ---- a GIVEN periodic edge list (csrc/graph.hip eqf_edges_pbc_count / eqf_edges_pbc_fill; by-source view: eqf_csr_by_source_multi)
+    @staticmethod
+    def edges_pbc_plan(pos, cell, batch, edge_index, cell_offsets, neighbors, num_graphs=None):
+        """The edge list an ocpmodels batch carries -- edge_index [2, E_in] = (neighbour, centre), integer cell_offsets [E_in, 3],
+        neighbors [B] = edges per structure, cell [B, 3, 3]; int64 or int32, read as they are -- through the count kernel
+        (Cartesian offsets, zero-length edges dropped: get_pbc_distances), the scans and the one host read-back: kept edges,
+        nodes of the largest structure, the sum of `neighbors` and the kernel's status word.  Nothing of an earlier graph is
+        touched.  Raises ValueError when `neighbors` does not sum to E_in or an edge names a node outside its structure."""
+        if not pos.is_cuda:
+            raise ops.HipOnlyError("graph construction runs on the GPU only")
+        p = EdgesPbcPlan()
+        p.pos = pos.detach().to(torch.float32).contiguous()
+        p.cell = cell.detach().to(device=p.pos.device, dtype=torch.float32).contiguous().view(-1, 3, 3)
+        p.N = int(p.pos.shape[0])
+        p.num_graphs = int(p.cell.shape[0]) if num_graphs is None else int(num_graphs)
+        dev = p.pos.device
+        ints = (torch.int64, torch.int32)
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype not in ints:
+            raise ValueError("edge_index must be a [2, E] int64 or int32 tensor, got %s %s" % (tuple(edge_index.shape), edge_index.dtype))
+        p.E_in = int(edge_index.shape[1])
+        if tuple(cell_offsets.shape) != (p.E_in, 3) or cell_offsets.dtype not in ints:
+            raise ValueError("cell_offsets must be a [%d, 3] int64 or int32 tensor, got %s %s"
+                             % (p.E_in, tuple(cell_offsets.shape), cell_offsets.dtype))
+        if neighbors.numel() != p.num_graphs or p.cell.shape[0] != p.num_graphs:
+            raise ValueError("neighbors has %d entries and cell %d, the batch has %d structures"
+                             % (neighbors.numel(), p.cell.shape[0], p.num_graphs))
+        # (no pass over the edges here: `.to` / `.contiguous()` of a contiguous device tensor return it as it is)
+        p.edge_index = edge_index.detach().to(dev).contiguous()
+        p.cell_offsets = cell_offsets.detach().to(dev).contiguous()
+        p.index64, p.offsets64 = int(edge_index.dtype == torch.int64), int(cell_offsets.dtype == torch.int64)
+        p.b32 = _i32(batch)
+        nb32 = neighbors.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()  # ([B]: not a per-edge pass)
+        st = _stream()
+        stats = torch.empty(4, dtype=torch.int32, device=dev)  # [E, nodes of the largest structure, sum of neighbors, status]
+        p.mol_ptr = torch.empty(p.num_graphs + 2, dtype=torch.int32, device=dev)  # (+ 1 entry: a phantom structure's end)
+        call("eqf_segment_ptr", _P(p.b32), p.N, p.num_graphs, _P(p.mol_ptr), _P(stats, 4), st)
+        p.nbr_ptr = torch.empty(p.num_graphs + 1, dtype=torch.int32, device=dev)
+        call("eqf_exclusive_scan_i32", _P(nb32), p.num_graphs, _P(p.nbr_ptr), _P(stats, 8), st)
+        p.keep = torch.empty(p.E_in, dtype=torch.uint8, device=dev)
+        p.off = torch.empty((p.E_in, 3), dtype=torch.float32, device=dev)
+        deg = torch.empty(p.N, dtype=torch.int32, device=dev)
+        call("eqf_edges_pbc_count", _P(p.pos), _P(p.cell), _P(p.mol_ptr), _P(p.nbr_ptr), p.num_graphs, p.N, _P(p.edge_index),
+             p.index64, _P(p.cell_offsets), p.offsets64, p.E_in, _P(p.keep), _P(p.off), _P(deg), _P(stats, 12), st)
+        p.row_ptr = torch.empty(p.N + 1, dtype=torch.int32, device=dev)
+        call("eqf_exclusive_scan_i32", _P(deg), p.N, _P(p.row_ptr), _P(stats), st)
+        p.E, p.max_mol_nodes, total, status = stats.tolist()  # the one host sync
+        if total != p.E_in:
+            raise ValueError("data.neighbors sums to %d, data.edge_index has %d edges" % (total, p.E_in))
+        if status:
+            raise ValueError("data.edge_index has an edge whose neighbour or centre lies outside the structure that data.neighbors "
+                             "assigns it to (status %d)" % status)
+        if p.max_mol_nodes > CSR_MAX_NODES:
+            raise ops.HipOnlyError("graphs from a given edge list need structures of at most %d nodes" % CSR_MAX_NODES)
+        return p
+
+    @staticmethod
+    def _edges_pbc_fill(plan, g):
+        """The E kept edges of `plan` into the head of g's per-edge tensors (row_ptr of the plan: real rows only)."""
+        call("eqf_edges_pbc_fill", _P(plan.mol_ptr), _P(plan.nbr_ptr), plan.num_graphs, int(plan.max_mol_nodes),
+             _P(plan.edge_index), plan.index64, _P(plan.cell_offsets), plan.offsets64, plan.E_in, _P(plan.keep), _P(plan.off),
+             _P(plan.row_ptr), plan.E, _P(g.src), _P(g.dst), _P(g.cell_offsets), _P(g.offsets), _P(g.order), _stream())
+
+    @staticmethod
+    def from_edges_pbc_plan(plan, capacity=None, into=None, z=None):
+        """Second half: the dst-sorted graph of the plan's kept edges, stable in input order.  Beside the index tensors the graph
+        owns `offsets` [E, 3] (fp32 Cartesian), `cell_offsets` [E, 3] (int32) and `order` [E] (int32: the input index of the edge in
+        each slot, for further per-edge data of the caller), and carries `_pbc = _radius_static = True`: every tensor is refilled
+        in place by enqueue-only kernels.
+
+        capacity=None: an exact-shape graph; `into` (a graph of this builder with the same node, structure and kept-edge counts)
+        is REWRITTEN in place and returned, with other counts the result is fresh and `into` is marked as abandoned.
+        capacity=(N_cap, E_cap): padded with one phantom structure exactly as `from_radius_pbc_plan` pads (the same padded
+        inputs, masks and host integers; `_padded`); phantom edges get zero rows in `offsets` / `cell_offsets` and -1 in `order`;
+        `into` is a padded graph of this builder with the same capacity and structure count.  Raises GraphDoesNotFit before
+        anything of `into` is written."""
+        N, E, B = plan.N, plan.E, plan.num_graphs
+        dev = plan.pos.device
+        st = _stream()
+        i32 = dict(dtype=torch.int32, device=dev)
+        given = into is not None and getattr(into, "order", None) is not None and getattr(into, "_pbc", False)
+        if capacity is None:
+            cand = given and not getattr(into, "_padded", False) and getattr(into, "_radius_static", False)
+            if cand and (into.N, into.E, into.num_graphs, into.src.device) == (N, E, B, dev):
+                g = into
+            else:
+                if cand:
+                    into._radius_static = False  # (abandoned: its owner falls back to an eager step on the fresh graph)
+                g = EdgeGraph.__new__(EdgeGraph)
+                g.N, g.E, g.num_graphs = N, E, B
+                g.src, g.dst, g.order = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
+                g.row_ptr, g.batch, g.mol_ptr = torch.empty(N + 1, **i32), torch.empty(N, **i32), torch.empty(B + 1, **i32)
+                g.src_perm, g.src_ptr = torch.empty(E, **i32), torch.empty(N + 1, **i32)
+                g.cell_offsets = torch.empty((E, 3), **i32)
+                g.offsets = torch.empty((E, 3), dtype=torch.float32, device=dev)
+                g._pbc = g._radius_static = True
+            with torch.no_grad():
+                g.row_ptr.copy_(plan.row_ptr)
+                g.mol_ptr.copy_(plan.mol_ptr[:B + 1])
+                g.batch.copy_(plan.b32)
+            EdgeGraph._edges_pbc_fill(plan, g)
+            call("eqf_csr_by_source_multi", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B, max(int(plan.max_mol_nodes), 1),
+                 _P(g.src_perm), _P(g.src_ptr), st)
+            return g
+        n_cap, e_cap = int(capacity[0]), int(capacity[1])
+        P, Q = n_cap - N, e_cap - E
+        if P < 0 or Q < 0 or P < min_phantom_nodes(Q):
+            raise GraphDoesNotFit("%d nodes / %d edges do not fit the capacity (%d, %d): %d phantom edges need %d phantom nodes"
+                                  % (N, E, n_cap, e_cap, max(Q, 0), min_phantom_nodes(max(Q, 0))))
+        if max(plan.max_mol_nodes, P) > CSR_MAX_NODES:
+            raise ops.HipOnlyError("padded periodic graphs need structures (the phantom one included) of at most %d nodes"
+                                   % CSR_MAX_NODES)
+        reuse = (given and getattr(into, "_padded", False) and into.N == n_cap and into.E == e_cap
+                 and into.num_graphs == B + 1 and into.src.device == dev and (into.z is None) == (z is None))
+        if reuse:
+            g = into
+        else:
+            g = EdgeGraph.__new__(EdgeGraph)
+            g.N, g.E, g.num_graphs = n_cap, e_cap, B + 1
+            g.src, g.dst, g.order = torch.empty(e_cap, **i32), torch.empty(e_cap, **i32), torch.empty(e_cap, **i32)
+            g.row_ptr, g.batch, g.mol_ptr = torch.empty(n_cap + 1, **i32), torch.empty(n_cap, **i32), torch.empty(B + 2, **i32)
+            g.src_perm, g.src_ptr = torch.empty(e_cap, **i32), torch.empty(n_cap + 1, **i32)
+            g.cell_offsets = torch.empty((e_cap, 3), **i32)
+            g.offsets = torch.empty((e_cap, 3), dtype=torch.float32, device=dev)
+            g.pos = torch.empty((n_cap, 3), dtype=torch.float32, device=dev)
+            g.z = torch.empty(n_cap, dtype=torch.int64, device=dev) if z is not None else None
+            g.node_mask = torch.empty(n_cap, dtype=torch.float32, device=dev)
+            g.graph_mask = torch.empty(B + 1, dtype=torch.float32, device=dev)
+            g._padded = g._radius_static = g._pbc = True
+            g.capacity = (n_cap, e_cap)
+        g.n_real, g.e_real, g.num_real_graphs = N, E, B
+        with torch.no_grad():
+            g.row_ptr[:N + 1].copy_(plan.row_ptr)
+            g.mol_ptr[:B + 1].copy_(plan.mol_ptr[:B + 1])
+            g.batch[:N].copy_(plan.b32)
+            g.pos[:N].copy_(plan.pos)
+            if z is not None:
+                g.z[:N].copy_(z)
+            if Q:
+                g.offsets[E:].zero_()
+                g.cell_offsets[E:].zero_()
+                g.order[E:].fill_(-1)
+        EdgeGraph._edges_pbc_fill(plan, g)
+        call("eqf_graph_pad_tail", N, E, n_cap, e_cap, B, _P(g.row_ptr), _P(g.src), _P(g.dst), _P(g.batch), _P(g.mol_ptr),
+             _P(g.pos), _P(g.z), _P(g.node_mask), _P(g.graph_mask), st)
+        call("eqf_csr_by_source_multi", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
+             _P(g.src_perm), _P(g.src_ptr), st)
+        return g
+
+    @staticmethod
+    def from_edges_pbc(pos, cell, batch, edge_index, cell_offsets, neighbors, num_graphs=None, into=None, capacity=None, z=None):
+        """`edges_pbc_plan` + `from_edges_pbc_plan`: returns (graph, offsets [E, 3] Cartesian, cell_offsets [E, 3] int32), the
+        conventions of `from_radius_pbc` for a batch that brings its own edge list (OC20 with otf_graph=False)."""
+        plan = EdgeGraph.edges_pbc_plan(pos, cell, batch, edge_index, cell_offsets, neighbors, num_graphs)
+        g = EdgeGraph.from_edges_pbc_plan(plan, capacity, into=into, z=z)
+        return g, g.offsets, g.cell_offsets
 
     @staticmethod
     def from_edges(edge_src, edge_dst, N, batch=None, num_graphs=None):

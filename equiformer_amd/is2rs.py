@@ -18,7 +18,7 @@ configuration uses them), and the OCP trainer around the step (loaders, EMA, eva
 import torch
 
 from . import ops
-from .capture import BucketedTrainStep
+from .capture import BucketedTrainStep, given_edge_fields
 from .dens import step_seed  # noqa: F401  (re-exported: the seed of step k)
 
 STATS = ("loss_e", "loss_aux", "n_free", "energy_mae", "energy_mse", "energy_within_threshold", "pos_mae", "unused")
@@ -105,7 +105,8 @@ class IS2RSTrainStep:
     generator is not touched, the caller's `pos` is not written.  With `total_steps` the loss's auxiliary device word is set to
     `auxiliary_task_weight(w0, k, total_steps)` before the step, w0 = the constructor's `auxiliary_task_weight` (default: the
     weight `loss` holds at construction).  The perturbed pos, y and the node targets tags, pos_relaxed then go to a periodic
-    `BucketedTrainStep` (bucket_kwargs: min_eager, max_graphs, node_step, edge_step, drop_path_seed -- default `seed`: step k of
+    `BucketedTrainStep` (bucket_kwargs: min_eager, max_graphs, node_step, edge_step, edges -- "batch": the batch's own edge_index,
+    cell_offsets, neighbors travel with it and the perturbation still comes first --, drop_path_seed -- default `seed`: step k of
     a model with drop_path_rate > 0 drops what an eager step under `droppath.device_draws(step_seed(seed, k))` drops) whose
     forward_loss is
     `model(view, graph=g, offsets=view.offsets)` and `loss(E[:view.B], vectors, view, row_mask=view.node_mask,
@@ -155,5 +156,8 @@ class IS2RSTrainStep:
             self.loss.set_weights(auxiliary_task_weight=auxiliary_task_weight(self.w0, k, self.total_steps))
         if "num_graphs" in batch:
             d["num_graphs"] = batch["num_graphs"]
+        if self.bucketed.edges == "batch":  # (the zero-length test of the given edges then sees the moved atoms, as the reference's)
+            for n in given_edge_fields(batch):
+                d[n] = batch[n]
         self.last = d
         return self.bucketed.step(d)

@@ -82,6 +82,9 @@ SIGNATURES = {
     "eqf_exclusive_scan_i32": [c_fp, c_int, c_fp, c_fp, c_fp],
     "eqf_csr_by_source": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp],
     "eqf_csr_by_source_multi": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp],
+    "eqf_edges_pbc_count": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_int, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "eqf_edges_pbc_fill": [c_fp, c_fp, c_int, c_int, c_fp, c_int, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp,
+                           c_fp, c_fp, c_fp],
     "eqf_graph_pad_tail": [c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "eqf_edge_geom_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
     "eqf_edge_geom_bwd": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp],

@@ -90,3 +90,20 @@ def oc20_like_varying_batches(num_batches, num_structures, atoms_range=(60, 96),
                         cell=torch.from_numpy(cells.astype(np.float32)), natoms=torch.from_numpy(natoms.astype(np.int64)),
                         num_graphs=int(num_structures), y=torch.from_numpy(rng.standard_normal(num_structures).astype(np.float32))))
     return out
+
+
+def attach_given_edges(batch, radius, max_num_neighbors=50):
+    """The fields an OC20 LMDB adds to a periodic batch (the reference's otf_graph=False contract), taken from the GPU neighbour
+    search (EdgeGraph.from_radius_pbc) at the given radius and cap: `edge_index` [2, E] int64 (neighbour, centre), `cell_offsets`
+    [E, 3] int64, `neighbors` [B] int64 (edges per structure).  batch: a dict of oc20_like_varying_batches with its tensors on the
+    GPU; returns a new dict on the same device (the tensors of `batch` are shared, not copied)."""
+    from .graph import EdgeGraph
+    B = int(batch["num_graphs"]) if "num_graphs" in batch else int(batch["cell"].reshape(-1, 3, 3).shape[0])
+    g, _, cell_offsets = EdgeGraph.from_radius_pbc(batch["pos"], batch["cell"], batch["batch"], radius,
+                                                   max_num_neighbors=max_num_neighbors, num_graphs=B)
+    ends = g.row_ptr.long()[g.mol_ptr.long()]  # first edge of every structure's first row, and the edge count
+    out = dict(batch)
+    out["edge_index"] = torch.stack([g.src.long(), g.dst.long()])
+    out["cell_offsets"] = cell_offsets.long()
+    out["neighbors"] = ends[1:] - ends[:-1]
+    return out

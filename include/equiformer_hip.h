@@ -123,6 +123,32 @@ int eqf_csr_by_source(const int* src, const int* row_ptr, const int* mol_ptr, in
 int eqf_csr_by_source_multi(const int* src, const int* row_ptr, const int* mol_ptr, int n_mol, int max_mol_nodes,
                             int* src_perm, int* src_ptr, void* stream);
 
+/* The periodic edge list a batch CARRIES (ocpmodels: edge_index[2, n_edges] = (neighbour j, centre i), integer images
+ * cell_offsets[n_edges, 3], `neighbors` = edges per structure) turned into the dst-sorted graph, without a device sort:
+ * both entry points only enqueue on the caller's stream (two memsets and one kernel; one kernel), allocate nothing and
+ * synchronise nothing -- legal between two replays of a captured step.  edge_index / cell_offsets are read as the
+ * loader stores them: 64-bit integers when index_is64 / offsets_is64 is non-zero, else 32-bit.  nbr_ptr[n_mol + 1] =
+ * exclusive scan of `neighbors`: structure b owns the input edges [nbr_ptr[b], nbr_ptr[b + 1]).
+ * [ref: nets/graph_attention_transformer_oc20.py:280-293 (_forward_use_pbc: get_pbc_distances(..., return_offsets=True));
+ *  un-vendored dependency, restated in oracle/pbc.py:get_pbc_distances]
+ * eqf_edges_pbc_count: per input edge e of structure b: off[e] = cell_offsets[e] @ cell[b] in fp32 ((n1 a1 + n2 a2) + n3 a3,
+ *   every operation rounded on its own, no FMA), vec = (pos[j] - pos[i]) + off[e], keep[e] = any(vec != 0) (zero-length
+ *   edges are dropped, as get_pbc_distances drops them), deg[n_nodes] = kept edges per centre (integer atomics).  j and i
+ *   are checked against [mol_ptr[b], mol_ptr[b + 1]) BEFORE anything is indexed with them; an edge that fails is not
+ *   kept, never dereferenced, and sets bit 0 of *status; an edge no structure owns sets bit 1.  *status = 0 otherwise.
+ * eqf_edges_pbc_fill: counting sort of the kept edges on the centre, stable in input order, given row_ptr = exclusive scan
+ *   of deg (n_kept = row_ptr[n_nodes]): slot = row_ptr[i] + (kept edges with the same centre earlier in the input).  One
+ *   workgroup per structure with per-node cursors in LDS, so max_mol_nodes <= 16384 (else EQF_E_UNSUPPORTED); the input
+ *   range is walked in passes of 256 edges.  Writes src / dst[n_kept], cell_offsets[n_kept, 3] (int32), offsets[n_kept, 3]
+ *   (fp32, off of the count) and order[n_kept] = the input index of the edge in each slot.                            */
+int eqf_edges_pbc_count(const float* pos, const float* cell, const int* mol_ptr, const int* nbr_ptr, int n_mol, int n_nodes,
+                        const void* edge_index, int index_is64, const void* cell_offsets, int offsets_is64, int n_edges,
+                        unsigned char* keep, float* off, int* deg, int* status, void* stream);
+int eqf_edges_pbc_fill(const int* mol_ptr, const int* nbr_ptr, int n_mol, int max_mol_nodes, const void* edge_index,
+                       int index_is64, const void* cell_offsets_in, int offsets_is64, int n_edges, const unsigned char* keep,
+                       const float* off, const int* row_ptr, int n_kept, int* src, int* dst, int* cell_offsets, float* offsets,
+                       int* order, void* stream);
+
 /* Pads a collated batch of n nodes / e dst-sorted edges / n_mol molecules to the capacity (n_cap, e_cap) its tensors
  * were allocated at, with ONE phantom molecule (index n_mol) that owns the P = n_cap - n tail nodes and the
  * Q = e_cap - e tail edges: a batch of any size then presents the shape of its bucket to the kernels (and to a
