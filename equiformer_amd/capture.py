@@ -23,6 +23,10 @@ What stays OUTSIDE the graph, and why:
     same masks as an eager loop under `device_draws(step_seed(drop_path_seed, k))`, padded or not (the draw of a graph does not
     depend on the number of graphs).  `drop_path_seed=None` draws the base seed from torch's CPU generator when the first
     GraphDropPath runs; a model without stochastic depth consumes nothing.
+  * the equivariant dropouts (`out_drop`, `proj_drop`: equiformer_amd/dropout.py) draw in the same scope from the same word:
+    `drop_path_seed` seeds both streams, which the kernels keep apart by stream tag (32 and 33) and the scope by two call
+    counters.  A step drops the entries `dropout.keep_mask(step_seed(drop_path_seed, k), call, rows, irreps, p)` names, on the
+    real rows of a padded batch as on the unpadded batch (the draw of a row does not depend on the number of rows).
 
 The MD17 force-loss step (forces by a create_graph backward inside the forward, then a second-order backward) is captured the
 same way (tests/test_gpu_capture.py; bench.py --workload md17_l2: 463 -> 619 frames/s, md17_l3: 218 -> 254).  The OC20 step on
@@ -47,7 +51,8 @@ class _DropPathWord:
     """The stochastic-depth seed of a step class: a device word that holds `dens.step_seed(seed, k)` during step k (k counts the
     steps of the instance from 0), written through a pinned buffer by an asynchronous copy.  seed None: the word holds
     `step_seed(0, k)` and the base seed travels by value (a constant: a capture may freeze it), drawn from torch's CPU generator
-    by the first GraphDropPath that really runs under the instance -- a model without stochastic depth consumes nothing."""
+    by the first GraphDropPath (or equivariant dropout: the same scope seeds both) that really runs under the instance -- a model
+    without stochastic depth and dropout consumes nothing."""
 
     def __init__(self, seed, device):
         self.seed = None if seed is None else int(seed)
@@ -91,7 +96,8 @@ class CapturedTrainStep:
     EdgeGraph of this step's batch (`EdgeGraph.from_radius(pos, batch, r, into=into)`, or for periodic structures
     `EdgeGraph.from_radius_pbc(pos, cell, batch, r, k, into=into)[0]`, whose `.offsets` forward_loss passes on), called OUTSIDE
     the capture.
-    optimizer: a FlatAdamW without a reducer.  drop_path_seed: the stochastic-depth seed (module docstring; None: drawn)."""
+    optimizer: a FlatAdamW without a reducer.  drop_path_seed: the seed of stochastic depth and of the equivariant dropouts
+    (module docstring; None: drawn)."""
 
     _drop_path = None  # the _DropPathWord the constructor makes (an instance built without it draws on the host, as before)
 

@@ -12,10 +12,21 @@ __device__ __forceinline__ unsigned long long eqf_mix64(unsigned long long z) {
 
 // 64 random bits of draw `idx` of stream `tag`: the tag is mixed into the seed first, so that two streams of one seed are
 // two different sequences, not one sequence at two offsets.
+// The two halves are separate functions for kernels that make many draws of one stream: the key depends on (seed, tag)
+// alone -- wave-uniform, formed once -- and a draw costs one mix of (key, idx).
+__device__ __forceinline__ unsigned long long eqf_rand_key(unsigned long long seed, unsigned long long tag) {
+  return eqf_mix64(seed + 0xD6E8FEB86659FD93ull * (tag + 1));
+}
+__device__ __forceinline__ unsigned long long eqf_rand_bits_keyed(unsigned long long key, unsigned long long idx) {
+  return eqf_mix64(key + 0x9E3779B97F4A7C15ull * (idx + 1));
+}
 __device__ __forceinline__ unsigned long long eqf_rand_bits(unsigned long long seed, unsigned long long tag,
                                                            unsigned long long idx) {
-  const unsigned long long key = eqf_mix64(seed + 0xD6E8FEB86659FD93ull * (tag + 1));
-  return eqf_mix64(key + 0x9E3779B97F4A7C15ull * (idx + 1));
+  return eqf_rand_bits_keyed(eqf_rand_key(seed, tag), idx);
+}
+// eqf_rand_uniform(seed, tag, idx) from the key of (seed, tag)
+__device__ __forceinline__ float eqf_rand_uniform_keyed(unsigned long long key, unsigned long long idx) {
+  return (float)(eqf_rand_bits_keyed(key, idx) >> 40) * (1.0f / 16777216.0f);
 }
 
 // uniform in [0, 1) from the top 24 bits (every value is an exact float: `u < 1.f` always, `u < 0.f` never)

@@ -105,7 +105,8 @@ def segment_droppath(x, seg_of, drop_prob, seed, call, seed_word=None):
 
 # ---- the scope ------------------------------------------------------------------------------------------------------------------
 class _Draws:
-    """The state of one `device_draws` scope: the seed (by value and / or device word) and the call counter."""
+    """The state of one `device_draws` scope: the seed (by value and / or device word) and the call counters -- one for
+    stochastic depth, one for the equivariant dropout (dropout.py), which draws from the same seed under another stream tag."""
 
     def __init__(self, seed, base):
         if torch.is_tensor(seed):
@@ -113,6 +114,7 @@ class _Draws:
         else:
             self.word, self._seed = None, int(seed)
         self.calls = 0
+        self.dropout_calls = 0  # the equivariant dropout's calls (dropout.py, stream tag 33) count apart from stochastic depth's
 
     @property
     def seed(self):
@@ -123,6 +125,11 @@ class _Draws:
     def next_call(self):
         c = self.calls
         self.calls += 1
+        return c
+
+    def next_dropout_call(self):
+        c = self.dropout_calls
+        self.dropout_calls += 1
         return c
 
 
@@ -139,8 +146,9 @@ def device_draws(seed, base=0):
     """Inside, a training-mode GraphDropPath with drop_prob > 0 draws its keep mask on the device.  seed: a Python int passed
     by value, or a one-element int64 CUDA tensor used as the device word (the by-value part is then `base`: 0, or a callable
     evaluated once by the first call that really drops -- the step classes' lazily drawn base seed).  The scope counts the
-    calls from 0: every GraphDropPath.forward that really drops takes the next value.  Scopes nest; leaving one restores the
-    outer scope with its counter."""
+    calls from 0: every GraphDropPath.forward that really drops takes the next value.  The equivariant dropout modules
+    (dropout.EquivariantDropout, EquivariantScalarsDropout: out_drop, proj_drop) draw in the kernel from the same seed in this
+    scope, counting their calls separately.  Scopes nest; leaving one restores the outer scope with its counters."""
     prev = _active[0]
     _active[0] = d = _Draws(seed, base)
     try:

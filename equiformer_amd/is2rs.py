@@ -107,7 +107,8 @@ class IS2RSTrainStep:
     weight `loss` holds at construction).  The perturbed pos, y and the node targets tags, pos_relaxed then go to a periodic
     `BucketedTrainStep` (bucket_kwargs: min_eager, max_graphs, node_step, edge_step, edges -- "batch": the batch's own edge_index,
     cell_offsets, neighbors travel with it and the perturbation still comes first --, drop_path_seed -- default `seed`: step k of
-    a model with drop_path_rate > 0 drops what an eager step under `droppath.device_draws(step_seed(seed, k))` drops) whose
+    a model with drop_path_rate > 0, out_drop > 0 (the 100k recipe) or proj_drop > 0 drops what an eager step under
+    `droppath.device_draws(step_seed(seed, k))` drops) whose
     forward_loss is
     `model(view, graph=g, offsets=view.offsets)` and `loss(E[:view.B], vectors, view, row_mask=view.node_mask,
     num_graphs=view.B)`.  The phantom rows of a padded batch have tag 0 and stay out of the loss through the row mask as well.

@@ -155,6 +155,7 @@ SIGNATURES = {
     "eqf_edgedeg_scatter_bwd": [c_fp, c_fp, c_fp, c_fp, _P_EDEG, _f, c_fp, c_fp, c_int, c_int, c_fp],
     "eqf_segment_scale": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
     "eqf_segment_droppath": [c_fp, c_fp, c_fp, c_int, c_int, _f, _f, _u64, c_fp, _u64, c_fp],
+    "eqf_irreps_dropout": [c_fp, c_fp, c_int, _P_IRR, c_int, _f, _f, _u64, c_fp, _u64, c_fp],
     "eqf_dtp_fwd": [c_fp, c_fp, c_fp, _P_PATHS, c_fp, c_int, c_fp],
     "eqf_dtp_bwd": [c_fp, c_fp, c_fp, _P_PATHS, c_fp, c_fp, c_fp, c_fp, c_int, c_fp],
     "eqf_alpha_fwd": [c_fp, c_fp, c_fp, c_int, c_int, c_int, _f, c_fp],

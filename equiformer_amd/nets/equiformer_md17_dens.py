@@ -58,6 +58,8 @@ class Equiformer_MD17_DeNS(GraphAttentionTransformerMD17):
         # registration order of the reference (parameters() order is what optimizer checkpoints index by)
         order = ["atom_embed", "rbf", "edge_deg_embed", "force_embed", "blocks", "norm", "energy_head", "scale_scatter",
                  "denoising_pos_head"]
+        if self.out_dropout is not None:  # parameter-free, registered behind the norm [ref: :140-142]
+            order.insert(order.index("norm") + 1, "out_dropout")
         assert sorted(order) == sorted(self._modules), sorted(self._modules)
         self._modules = {k: self._modules[k] for k in order}
 
@@ -84,6 +86,7 @@ class Equiformer_MD17_DeNS(GraphAttentionTransformerMD17):
         second_order = self.training and trainable
         self.__dict__["_second_order_pass"] = second_order
         node_features, ectx = self._trunk_features(atom_embedding, pos, graph, extra=force_embedding)
+        node_features = self._out_drop(node_features)  # both heads read the dropped features [ref: :307-309, :333-334]
         energy = self.energy_head(node_features)
         if hasattr(data, "denoising_mask") and not self.use_force_encoding:  # [ref: :309-311]
             energy = energy * (~data.denoising_mask).to(energy.dtype).view(-1, 1)

@@ -9,6 +9,7 @@ from torch import nn
 
 from .. import ops
 from ..graph import EdgeGraph
+from ..dropout import EquivariantDropout
 from ..irreps import Irreps
 from .layers import (Activation, EdgeContext, EdgeDegreeEmbeddingNetwork, EquivariantGraphNorm,  # noqa: F401
                      EquivariantInstanceNorm, EquivariantLayerNormV2, FeedForwardNetwork, FullyConnectedTensorProductRescale, GaussianRadialBasisLayer, GraphAttention,
@@ -31,8 +32,6 @@ class _Trunk(nn.Module):
                      number_of_basis, fc_neurons, irreps_feature, irreps_head, num_heads, irreps_pre_attn,
                      rescale_degree, nonlinear_message, irreps_mlp_mid, norm_layer, alpha_drop, proj_drop, out_drop,
                      drop_path_rate, max_atom_type, avg_degree, avg_num_nodes):
-        if out_drop != 0.0:
-            raise NotImplementedError("out_drop != 0 is not used by any registered model")
         self.max_radius = max_radius
         self.number_of_basis = number_of_basis
         self.alpha_drop, self.proj_drop, self.out_drop = alpha_drop, proj_drop, out_drop
@@ -69,7 +68,8 @@ class _Trunk(nn.Module):
                 proj_drop=proj_drop, drop_path_rate=drop_path_rate, irreps_mlp_mid=self.irreps_mlp_mid,
                 norm_layer=norm_layer))
         self.norm = get_norm_layer(norm_layer)(self.irreps_feature)
-        self.out_dropout = None
+        # between the final norm and the head [ref: :797-799, :891-892]; the OC20 models drop the scalar channels only
+        self.out_dropout = self._out_dropout_cls(self.irreps_feature, self.out_drop) if self.out_drop != 0.0 else None
         if all(ir.l == 0 for _, ir in self.irreps_feature):  # otherwise the subclass brings its own head (OC20)
             self.head = nn.Sequential(
                 LinearRS(self.irreps_feature, self.irreps_feature, rescale=_RESCALE),
@@ -128,6 +128,11 @@ class _Trunk(nn.Module):
 
     use_radial_bank = True
     _block_cls = TransBlock
+    _out_dropout_cls = EquivariantDropout
+
+    def _out_drop(self, node_features):
+        """the normed features as the head reads them: `out_drop` applied (the identity in eval mode and at rate 0)"""
+        return node_features if self.out_dropout is None else self.out_dropout(node_features)
 
     def late_gradient_parameters(self):
         """Parameters whose gradient is complete only at the end of backward although they belong to late layers: the
@@ -142,6 +147,7 @@ class _Trunk(nn.Module):
 
     def _trunk_forward(self, node_embedding, pos, graph, offsets=None):
         node_features, ectx = self._trunk_features(node_embedding, pos, graph, offsets)
+        node_features = self._out_drop(node_features)
         if isinstance(self.head, GraphAttention):  # attention head (MD17 use_attn_head)
             outputs = self.head(node_features, ectx=ectx)
         else:

@@ -6,12 +6,14 @@ The reference registers the class in ocpmodels' registry as "graph_attention_tra
 (`pos, batch, atomic_numbers, tags, natoms, cell`, and with `otf_graph=False` the precomputed `edge_index, cell_offsets,
 neighbors` of an ocpmodels batch -- see `_graph` for the exact contract; with `otf_graph=True` the periodic neighbour search
 runs on the GPU, `EdgeGraph.from_radius_pbc`).  The auxiliary IS2RS head
-(`use_auxiliary_task`, the `*_aux_*` configs), the attention head (`use_attention_head`) and per-graph stochastic depth
-(`drop_path_rate`) are built as upstream; atom-edge attributes and node attributes are used by no shipped config and are
+(`use_auxiliary_task`, the `*_aux_*` configs), the attention head (`use_attention_head`), per-graph stochastic depth
+(`drop_path_rate`) and the dropouts `out_drop` (scalar channels in front of the energy head, the 100k configs) and
+`proj_drop` (equiformer_amd/dropout.py) are built as upstream; atom-edge attributes and node attributes are used by no shipped config and are
 rejected.
 """
 import torch
 
+from ..dropout import EquivariantScalarsDropout
 from ..graph import EdgeGraph
 from ..irreps import Irreps
 from .graph_attention_transformer import _RESCALE, _Trunk
@@ -26,6 +28,8 @@ _AVG_DEGREE = 23.395238876342773
 
 
 class GraphAttentionTransformerOC20(_Trunk):
+    _out_dropout_cls = EquivariantScalarsDropout  # [ref: :165-167]
+
     def __init__(self, num_atoms=None, bond_feat_dim=None, num_targets=1, irreps_node_embedding="256x0e+128x1e",
                  num_layers=6, irreps_node_attr="1x0e", use_node_attr=False, irreps_sh="1x0e+1x1e", max_radius=6.0,
                  number_of_basis=128, fc_neurons=[64, 64], use_atom_edge_attr=False, irreps_atom_edge_attr="8x0e",
@@ -146,13 +150,14 @@ class GraphAttentionTransformerOC20(_Trunk):
         tag_embedding, _, _ = self.tag_embed(data.tags.long())
         node_features, ectx = self._trunk_features(atom_embedding + tag_embedding, pos, graph, offsets)
         scatter = lambda t: self.scale_scatter(t, graph.mol_ptr, graph.batch, graph.num_graphs)  # noqa: E731
-        if self.use_attention_head:  # [ref: :352-366]
-            outputs = self.head(node_features, ectx=ectx) + self.head_skip_connect(node_features)
+        dropped = self._out_drop(node_features)  # out_drop on the scalar channels [ref: :345-348]
+        if self.use_attention_head:  # [ref: :352-366] head and skip connection both read the dropped features
+            outputs = self.head(dropped, ectx=ectx) + self.head_skip_connect(dropped)
             if self.use_auxiliary_task:
                 return scatter(outputs.narrow(1, 0, 1).contiguous()), outputs.narrow(1, 1, 3)
             return scatter(outputs)
-        energy = scatter(self.head(node_features))
-        if self.use_auxiliary_task:  # [ref: :372-379]
+        energy = scatter(self.head(dropped))
+        if self.use_auxiliary_task:  # [ref: :372-379] the auxiliary head reads the UN-dropped features
             return energy, self.auxiliary_head(node_features, ectx=ectx)
         return energy
 
@@ -188,6 +193,15 @@ def oc20_l1_256_nonlinear_aux(**over):
     cfg = dict(irreps_feature="512x0e+256x1e", drop_path_rate=0.05, use_auxiliary_task=True)
     cfg.update(over)
     return oc20_l1_256_nonlinear(**cfg)
+
+
+@register_model
+def oc20_l1_256_nonlinear_aux_100k(**over):
+    """oc20/configs/is2re/100k/graph_attention_transformer/l1_256_nonlinear_aux_g@2_local.yml: the IS2RE-100k recipe of the same
+    model -- attention dropout 0.1, dropout 0.1 on the scalar channels in front of the energy head, no stochastic depth."""
+    cfg = dict(alpha_drop=0.1, out_drop=0.1, drop_path_rate=0.0)
+    cfg.update(over)
+    return oc20_l1_256_nonlinear_aux(**cfg)
 
 
 @register_model

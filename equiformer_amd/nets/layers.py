@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from .. import droppath, ops, so3
+from ..dropout import EquivariantDropout
 from ..irreps import Irrep, Irreps
 from ..layout import DtpTable, RowLayout
 
@@ -610,8 +611,6 @@ class GraphAttention(nn.Module):
         self.nonlinear_message = nonlinear_message
         if rescale_degree:
             raise NotImplementedError("rescale_degree=True is not used by any registered model")
-        if proj_drop != 0.0:
-            raise NotImplementedError("proj_drop != 0 is not used by any registered model")
 
         self.merge_src = LinearRS(self.irreps_node_input, self.irreps_pre_attn, bias=True)
         self.merge_dst = LinearRS(self.irreps_node_input, self.irreps_pre_attn, bias=False)
@@ -661,7 +660,10 @@ class GraphAttention(nn.Module):
         self.alpha_drop = float(alpha_drop)
         self.alpha_dropout = nn.Dropout(alpha_drop) if alpha_drop != 0.0 else None  # marker module (no params)
         self.proj = LinearRS(irreps_attn_heads, self.irreps_node_output)
-        self.proj_drop = None
+        # [ref: :476-479] the reference sizes the dropout with irreps_node_input: the same irreps in every block.  Where they
+        # differ (an attention head built with proj_drop != 0: the MD17 / DeNS heads) its product with the projected rows
+        # fails on the shapes; here the dropout is sized with the rows it multiplies.
+        self.proj_drop = EquivariantDropout(self.irreps_node_output, proj_drop) if proj_drop != 0.0 else None
         self.use_fused = True
 
     def forward(self, node_input, node_attr=None, edge_src=None, edge_dst=None, edge_attr=None, edge_scalars=None,
@@ -682,7 +684,10 @@ class GraphAttention(nn.Module):
             drop_p = self.alpha_drop
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
         attn = ops.attn_aggregate(logit, value, g, self.num_heads, self.heads_layout, drop_p, seed)
-        return self.proj(attn)
+        node_output = self.proj(attn)
+        if self.proj_drop is not None:  # [ref: :524-525]
+            node_output = self.proj_drop(node_output)
+        return node_output
 
     def radial_module(self):
         """The RadialProfile evaluated on the shared radial basis (a member of the model's RadialBank)."""
@@ -751,8 +756,6 @@ class DotProductAttention(nn.Module):
         self.rescale_degree = rescale_degree
         if rescale_degree:
             raise NotImplementedError("rescale_degree=True is not used by any registered model")
-        if proj_drop != 0.0:
-            raise NotImplementedError("proj_drop != 0 is not used by any registered model")
         if [ir.l for _, ir in self.irreps_head] != sorted({ir.l for _, ir in self.irreps_head}):
             raise NotImplementedError("irreps_head must list each degree once, in ascending order")
         irreps_attn_heads = _simplified_sorted(self.irreps_head * num_heads)
@@ -766,7 +769,8 @@ class DotProductAttention(nn.Module):
         self.alpha_drop = float(alpha_drop)
         self.alpha_dropout = nn.Dropout(alpha_drop) if alpha_drop != 0.0 else None  # marker module (no params)
         self.proj = LinearRS(irreps_attn_heads, self.irreps_node_output)
-        self.proj_drop = None
+        # [ref: nets/dp_attention_transformer.py:116-119]
+        self.proj_drop = EquivariantDropout(self.irreps_node_output, proj_drop) if proj_drop != 0.0 else None
         self.use_fused = True
 
     def radial_module(self):
@@ -785,7 +789,10 @@ class DotProductAttention(nn.Module):
             drop_p = self.alpha_drop
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
         attn = ops.attn_aggregate(logit, v, g, H, self.heads_layout, drop_p, seed)
-        return self.proj(attn)
+        node_output = self.proj(attn)
+        if self.proj_drop is not None:  # [ref: nets/dp_attention_transformer.py:156-157]
+            node_output = self.proj_drop(node_output)
+        return node_output
 
     def extra_repr(self):
         return "rescale_degree={}".format(self.rescale_degree)
@@ -794,8 +801,6 @@ class DotProductAttention(nn.Module):
 class FeedForwardNetwork(nn.Module):
     def __init__(self, irreps_node_input, irreps_node_attr, irreps_node_output, irreps_mlp_mid=None, proj_drop=0.1):
         super().__init__()
-        if proj_drop != 0.0:
-            raise NotImplementedError("proj_drop != 0 is not used by any registered model")
         self.irreps_node_input = Irreps(irreps_node_input)
         self.irreps_node_attr = Irreps(irreps_node_attr)
         self.irreps_mlp_mid = Irreps(irreps_mlp_mid) if irreps_mlp_mid is not None else self.irreps_node_input
@@ -804,10 +809,14 @@ class FeedForwardNetwork(nn.Module):
                                                                   self.irreps_mlp_mid, bias=True, rescale=_RESCALE)
         self.fctp_2 = FullyConnectedTensorProductRescale(self.irreps_mlp_mid, self.irreps_node_attr,
                                                          self.irreps_node_output, bias=True, rescale=_RESCALE)
-        self.proj_drop = None
+        # [ref: :560-563]
+        self.proj_drop = EquivariantDropout(self.irreps_node_output, proj_drop) if proj_drop != 0.0 else None
 
     def forward(self, node_input, node_attr=None, **kwargs):
-        return self.fctp_2(self.fctp_1(node_input, node_attr), node_attr)
+        node_output = self.fctp_2(self.fctp_1(node_input, node_attr), node_attr)
+        if self.proj_drop is not None:  # [ref: :569-570]
+            node_output = self.proj_drop(node_output)
+        return node_output
 
 
 class GraphDropPath(nn.Module):

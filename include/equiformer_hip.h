@@ -574,6 +574,24 @@ int eqf_segment_droppath(const float* x, const int* seg_of, float* out, int rows
                          unsigned long long seed, const unsigned long long* seed_word, unsigned long long call,
                          void* stream);
 
+/* Equivariant dropout with the mask DRAWN on the device.  x, out: [rows, D] rows of `ir` (CF layout).  Irrep instance
+ * (segment s, channel u) of a row has the channel index c = sum_{s' < s} mul[s'] + u (counted over all segments), and
+ *   out[row, s, m, u] = f(row, c) * x[row, s, m, u]   for every component m: one factor per irrep instance,
+ *   f(row, c) = u01 >= drop_p ? inv_keep : 0,   u01 = the uniform of csrc/rng.h for
+ *   seed + (seed_word ? *seed_word : 0) (mod 2^64), stream tag 33, index (call << 48) | (row << 16) | c.
+ * scalars_only != 0: only the 0e segments (l == 0, even) are dropped; every other segment, 0o included, is copied bit
+ * for bit.  inv_keep: 1 / (1 - drop_p), rounded to fp32 by the caller.  seed_word: a device word (may be NULL) that the
+ * host advances between the replays of a captured step; call: which dropout call of the step this is.  A pure function
+ * of (total seed, call, row, c) -- independent of the launch geometry and of `rows` -- and linear in x: its backward
+ * and second-order term are the same call on dy with the same (seed, seed_word, call).  A multiply, never a select
+ * (a NaN stays a NaN, a dropped entry is +-0).  out must not overlap x.
+ * Every mul % 4 == 0, sum mul < 2^16 and call < 2^16 (else EQF_E_UNSUPPORTED before any launch, out untouched);
+ * rows <= 0 launches nothing.
+ * [ref: nets/drop.py:68-108 EquivariantDropout, EquivariantScalarsDropout] */
+int eqf_irreps_dropout(const float* x, float* out, int rows, const eqf_irreps* ir, int scalars_only, float drop_p,
+                       float inv_keep, unsigned long long seed, const unsigned long long* seed_word,
+                       unsigned long long call, void* stream);
+
 /* Depth-wise tensor product, un-fused form (kept as the building block for shapes the fused GEMM
  * does not cover and as its on-device cross-check): out[e, :] per eqf_dtp_paths.  w may be NULL.
  * [ref: DepthwiseTensorProduct + o3.TensorProduct('uvu'), nets/graph_attention_transformer.py:157-183] */

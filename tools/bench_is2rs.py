@@ -3,6 +3,7 @@
 
     python tools/bench_is2rs.py [--batches 48] [--regions 3] [--out profiles/is2rs_step.json]
     python tools/bench_is2rs.py --drop-path-rate 0.05 --out profiles/is2rs_step_droppath.json
+    python tools/bench_is2rs.py --out-drop 0.1 --out profiles/is2rs_step_outdrop.json
 
 The `l1_256_nonlinear_aux` model (6 blocks, feature 512x0e+256x1e, IS2RS head; drop_path_rate 0 unless --drop-path-rate says
 otherwise, see the end), 16 slab structures of 60-96 atoms per batch
@@ -25,6 +26,13 @@ batches in one run, one model:
   `eager_host`:    (B) with the mask drawn from torch's CPU generator and uploaded, call by call -- the only way to train this
                    configuration without the device draw;
   `captured_p0`:   IS2RSTrainStep with the rate set to 0 while its graphs are captured: what stochastic depth costs a replay.
+
+--out-drop P > 0 (the IS2RE-100k recipe `l1_256_nonlinear_aux_100k`: 0.1) times the dropout on the scalar channels in front of the
+energy head (equiformer_amd/dropout.py), four legs over the same batches in one run, one model:
+  `captured`:      IS2RSTrainStep, the mask drawn in eqf_irreps_dropout from the step's device word;
+  `eager`:         (B) under droppath.device_draws(step_seed(seed, k)): the same draws, launched from the host;
+  `captured_p0`, `eager_p0`: the same two with out_drop set to 0 while the step is launched or captured: what the dropout costs;
+and the operator alone beside eqf_segment_scale at the feature shape (`dropout_alone`).
 Prints one JSON line."""
 import argparse
 import json
@@ -40,6 +48,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 MODEL = "oc20_l1_256_nonlinear_aux"
+MODEL_100K = "oc20_l1_256_nonlinear_aux_100k"    # the IS2RE-100k recipe: alpha_drop 0.1, out_drop 0.1, no stochastic depth
 RADIUS, MAX_NEIGHBORS = 5.0, 500
 W0 = 15.0                                    # auxiliary_task_weight of the shipped _aux configurations
 E_MEAN, E_STD = -1.5, 2.3                    # stand-in statistics
@@ -172,6 +181,128 @@ def stochastic_depth_legs(args, rate, batches, B, lib, ts, ts0, L, legs):
             fh.write(line + "\n")
 
 
+def dropout_alone(rate, rows=1248, irreps="512x0e+256x1e", graphs=16, launches=200, repeats=9):
+    """eqf_irreps_dropout alone at the OC20 feature shape (16 structures of 78 atoms x 512x0e+256x1e, D = 1280) beside
+    eqf_segment_scale -- an existing kernel that moves the same bytes -- in one process.  Two ways, both with device events
+    around `launches` launches, the operators alternating, `repeats` blocks after one untimed block each: launched back to back
+    through the Python operators (includes the host's launch rate), and the same launches replayed from one captured HIP graph
+    per operator (the device's own pace).  Microseconds per launch: median, p10 and p90 over the blocks."""
+    from equiformer_amd import dropout, droppath, ops
+    from equiformer_amd.layout import RowLayout
+    dev = torch.device("cuda:0")
+    lay = RowLayout(irreps)
+    x = torch.randn(rows, lay.dim, device=dev)
+    seg = torch.repeat_interleave(torch.arange(graphs, dtype=torch.int32), rows // graphs).to(dev)
+    f = droppath.keep_factors(0, 0, graphs, rate).to(dev)
+    fns = {"irreps_dropout_scalars": lambda: dropout.irreps_dropout(x, lay, rate, 0, 0, scalars_only=True),
+           "irreps_dropout_all": lambda: dropout.irreps_dropout(x, lay, rate, 0, 0),
+           "segment_scale": lambda: ops.segment_scale(x, f, seg)}
+    for so in (True, False):
+        want = x * dropout.keep_mask(0, 0, rows, lay, rate, so, expand="cf").to(dev)
+        assert torch.equal(fns["irreps_dropout_scalars" if so else "irreps_dropout_all"](), want)
+
+    def timed(run):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        run()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3 / launches
+
+    def many(fn):
+        for _ in range(launches):
+            fn()
+
+    def stats(v):
+        s = sorted(v)
+        q = lambda p: s[min(len(s) - 1, int(round(p * (len(s) - 1))))]  # noqa: E731
+        return {"median": q(0.5), "p10": q(0.1), "p90": q(0.9)}
+
+    eager = {k: [] for k in fns}
+    for _ in range(repeats + 1):  # (the first block of each: untimed warm-up)
+        for k, fn in fns.items():
+            eager[k].append(timed(lambda: many(fn)))
+    out = {"rows": rows, "irreps": irreps, "D": lay.dim, "bytes_moved": 8 * rows * lay.dim, "launches_per_block": launches, "blocks": repeats,
+           "us_per_launch": {k: stats(v[1:]) for k, v in eager.items()},
+           "how": "device events around %d launches, the operators alternating, %d blocks after one untimed block; us_per_launch: back "
+                  "to back through the Python operators (includes the host's launch rate); us_per_launch_in_graph: the same launches "
+                  "replayed from one captured HIP graph per operator" % (launches, repeats)}
+    try:  # (a capture that does not come up must not cost the other timings)
+        graphs_of, replay = {}, {k: [] for k in fns}
+        side = torch.cuda.Stream()
+        for k, fn in fns.items():
+            with torch.cuda.stream(side):
+                many(fn)  # (warm-up on the capture stream: allocator and kernels loaded)
+                torch.cuda.synchronize()
+                graphs_of[k] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs_of[k], stream=side):
+                    many(fn)
+            torch.cuda.synchronize()
+        for _ in range(repeats + 1):
+            for k in fns:
+                replay[k].append(timed(graphs_of[k].replay))
+        out["us_per_launch_in_graph"] = {k: stats(v[1:]) for k, v in replay.items()}
+    except Exception as exc:
+        out["us_per_launch_in_graph_error"] = "%s: %s" % (type(exc).__name__, exc)
+    for key in ("us_per_launch", "us_per_launch_in_graph"):
+        if key not in out:
+            continue
+        d, s = out[key]["irreps_dropout_scalars"], out[key]["segment_scale"]
+        out[key]["ratio_scalars_over_segment_scale"] = d["median"] / s["median"]
+        out[key]["p10_p90_overlap"] = d["p10"] <= s["p90"] and s["p10"] <= d["p90"]
+    return out
+
+
+def out_drop_legs(args, rate, batches, B, lib, ts, ts0, L, legs):
+    """--out-drop > 0: the four legs of the module docstring, timed as the default run times its three"""
+    def one_pass(step):
+        out = []
+        for d in batches:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step(d)
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return out
+
+    for name, step in legs:  # untimed: one pass of the eager legs, min_eager + 1 of the captured ones (every bucket has its graph)
+        for _ in range(ts.bucketed.min_eager + 1 if name.startswith("captured") else 1):
+            one_pass(step)
+    warm = {n: dict(eager_steps=t.eager_steps, captures=t.captures, replays=t.replays) for n, t in (("captured", ts), ("captured_p0", ts0))}
+    ms = {name: [] for name, _ in legs}
+    for _ in range(args.regions):
+        for name, step in legs:
+            ms[name] += one_pass(step)
+    res = {name: summary(v, B) for name, v in ms.items()}
+    out = {
+        "what": "IS2RE + IS2RS train step with dropout on the scalar channels in front of the energy head, %s (alpha_drop 0.1, out_drop "
+                "%g, no stochastic depth), %d different batches of %d slab structures (%d-%d atoms), r=%.1f, max_neighbors=%d, split "
+                "mode, one process, one model; device-synchronised wall time per step, one region = one pass over all batches, legs "
+                "alternating; the _p0 legs: the same model with out_drop set to 0 while its steps are launched or captured"
+                % (MODEL_100K, rate, len(batches), B, args.atoms_min, args.atoms_max, RADIUS, MAX_NEIGHBORS),
+        "build": lib.built_hash(), "regions": args.regions, "out_drop": rate,
+    }
+    out.update(res)
+    for name in res:
+        out[name + "_range_ms"] = res[name]["p90_ms"] - res[name]["p10_ms"]
+    out["captured_over_eager"] = res["eager"]["median_ms"] / res["captured"]["median_ms"]
+    out["cost_over_captured_p0_ms"] = res["captured"]["median_ms"] - res["captured_p0"]["median_ms"]
+    out["cost_over_eager_p0_ms"] = res["eager"]["median_ms"] - res["eager_p0"]["median_ms"]
+    out["operator_alone"] = dropout_alone(rate)
+    out["warmup"] = warm
+    out["captured_timed"] = {n: dict(eager_steps=t.eager_steps - warm[n]["eager_steps"], captures=t.captures - warm[n]["captures"],
+                                     replays=t.replays - warm[n]["replays"], live_graphs=len(t.bucketed.live_graphs()))
+                             for n, t in (("captured", ts), ("captured_p0", ts0))}
+    out["last_stats"] = dict(zip(("loss_e", "loss_aux", "n_free", "energy_mae", "energy_mse", "energy_within_threshold", "pos_mae"),
+                                 L.stats.cpu().tolist()))
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=48)
@@ -183,6 +314,7 @@ def main():
     ap.add_argument("--edge-step", type=int, default=2048)
     ap.add_argument("--max-graphs", type=int, default=16)
     ap.add_argument("--drop-path-rate", type=float, default=0.0)
+    ap.add_argument("--out-drop", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "is2rs_step.json"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_is2rs.py needs an MI355X"
@@ -197,7 +329,12 @@ def main():
     B = args.structures
     assert ops.get_matrix_mode() == "split"
     rate = float(args.drop_path_rate)
-    model = nets.model_entrypoint(MODEL)(drop_path_rate=rate).to(dev).train()
+    out_drop = float(args.out_drop)
+    assert not (rate > 0.0 and out_drop > 0.0), "--drop-path-rate and --out-drop are two runs"
+    if out_drop > 0.0:
+        model = nets.model_entrypoint(MODEL_100K)(out_drop=out_drop).to(dev).train()
+    else:
+        model = nets.model_entrypoint(MODEL)(drop_path_rate=rate).to(dev).train()
     drop_modules = [m for m in model.modules() if isinstance(m, GraphDropPath)]
 
     def set_rate(p):  # (read when a step is launched from the host: an eager step or a capture, never a replay)
@@ -237,6 +374,28 @@ def main():
         opt.step()
 
     legs = [("aten", step_aten), ("fused", step_fused), ("captured", ts.step)]
+    if out_drop > 0.0:
+        ts0 = IS2RSTrainStep(model, opt, L, RADIUS, MAX_NEIGHBORS, interpolate=True, seed=0, total_steps=total_steps,
+                             auxiliary_task_weight=W0, node_step=args.node_step, edge_step=args.edge_step,
+                             max_graphs=args.max_graphs)
+        counter["device"] = 0
+
+        def step_eager(d):  # (the draws of the captured leg, launched from the host)
+            with droppath.device_draws(step_seed(0, counter["device"])):
+                counter["device"] += 1
+                step_fused(d)
+
+        def at_rate_zero(step):  # (the rate is read when a step is launched from the host: an eager step or a capture, never a replay)
+            def run(d):
+                model.out_dropout.drop_prob = 0.0
+                try:
+                    step(d)
+                finally:
+                    model.out_dropout.drop_prob = out_drop
+            return run
+        return out_drop_legs(args, out_drop, batches, B, lib, ts, ts0, L,
+                             [("captured", ts.step), ("eager", step_eager), ("captured_p0", at_rate_zero(ts0.step)),
+                              ("eager_p0", at_rate_zero(step_eager))])
     if rate > 0.0:
         ts0 = IS2RSTrainStep(model, opt, L, RADIUS, MAX_NEIGHBORS, interpolate=True, seed=0, total_steps=total_steps,
                              auxiliary_task_weight=W0, node_step=args.node_step, edge_step=args.edge_step,
