@@ -19,7 +19,7 @@ What stays OUTSIDE the graph, and why:
     (eqf_adamw_step_dev); the host writes them (pinned buffer, asynchronous copy) before it launches the graph.
   * per-graph stochastic depth (`drop_path_rate > 0`) likewise: the step classes run every step, eager or captured, inside
     `droppath.device_draws(word)`, so GraphDropPath draws its keep mask in the kernel (eqf_segment_droppath) from a second
-    device word that holds `dens.step_seed(drop_path_seed, k)` during step k of the instance -- a fresh mask per replay, the
+    device word that holds `droppath.step_seed(drop_path_seed, k)` during step k of the instance -- a fresh mask per replay, the
     same masks as an eager loop under `device_draws(step_seed(drop_path_seed, k))`, padded or not (the draw of a graph does not
     depend on the number of graphs).  `drop_path_seed=None` draws the base seed from torch's CPU generator when the first
     GraphDropPath runs; a model without stochastic depth consumes nothing.
@@ -39,25 +39,54 @@ builders only -- from positions (`from_radius`, `from_radius_pbc`) or from the p
 (`from_edges_pbc`: otf_graph=False; the step classes take it with `edges="batch"`); an arbitrary edge list without the
 `neighbors` / `cell_offsets` contract still goes through EdgeGraph.from_edges and its device sort: eager --, structures of at most
 `graph.CSR_MAX_NODES` nodes, inputs other than the graph at fixed addresses (`forward_loss` reads the same tensors every step;
-copy a new batch into them)."""
+copy a new batch into them).
+
+How the classes are put together: `_CapturingStep` holds the capture protocol (record, file the record, words out, first replay)
+and the replay, with the optimizer's share of both left out where there is no optimizer; `_TrainStep` adds what a train step
+is made of (the eager step that is also what a capture records, the dropout seed word, the stochastic-depth word);
+`_BucketedStep` adds the bucket records and the one `step` of the bucketed classes, which BucketedTrainStep and
+evaluate.BucketedEvalStep complete with `_run`, their pre-checks, the words they send and how a record's outputs are returned.
+`_DeviceWord` is the pinned host word + device word + asynchronous copy that every such number travels through."""
+import collections
 import contextlib
+import functools
 
 import torch
 
 from . import droppath, ops
+from .droppath import step_seed
+from .graph import EdgeGraph, min_phantom_nodes
 
 
-class _DropPathWord:
-    """The stochastic-depth seed of a step class: a device word that holds `dens.step_seed(seed, k)` during step k (k counts the
-    steps of the instance from 0), written through a pinned buffer by an asynchronous copy.  seed None: the word holds
-    `step_seed(0, k)` and the base seed travels by value (a constant: a capture may freeze it), drawn from torch's CPU generator
-    by the first GraphDropPath (or equivariant dropout: the same scope seeds both) that really runs under the instance -- a model
-    without stochastic depth and dropout consumes nothing."""
+class _DeviceWord:
+    """One int64 that captured launches read from device memory (`.dev`), written by the host through a pinned word (`.host`) and
+    an asynchronous copy.  (The graph build's host read-back follows every write and waits for it: the pinned word is free
+    again when the next step writes it.)"""
 
-    def __init__(self, seed, device):
-        self.seed = None if seed is None else int(seed)
+    def __init__(self, device):
         self.dev = torch.zeros(1, dtype=torch.int64, device=device)
         self.host = torch.zeros(1, dtype=torch.int64).pin_memory()
+
+    def write(self, v):
+        self.host[0] = v
+        self.dev.copy_(self.host, non_blocking=True)
+
+
+def _draw_seed(word):
+    """a fresh seed offset of the attention dropout into its device word"""
+    word.write(int(torch.randint(0, 2 ** 62, (1,)).item()))  # CPU generator, as the eager layers draw theirs
+
+
+class _DropPathWord(_DeviceWord):
+    """The stochastic-depth seed of a step class: a device word that holds `step_seed(seed, k)` during step k (k counts the
+    steps of the instance from 0).  seed None: the word holds `step_seed(0, k)` and the base seed travels by value (a
+    constant: a capture may freeze it), drawn from torch's CPU generator by the first GraphDropPath (or equivariant dropout:
+    the same scope seeds both) that really runs under the instance -- a model without stochastic depth and dropout consumes
+    nothing."""
+
+    def __init__(self, seed, device):
+        super().__init__(device)
+        self.seed = None if seed is None else int(seed)
         self.k = 0
         self._drawn = None
 
@@ -67,13 +96,10 @@ class _DropPathWord:
         return self._drawn
 
     def advance(self):
-        """the word of the next step goes out (the graph build's host read-back follows and waits for it: the pinned buffer is
-        free again when the next step writes it)"""
-        from .dens import step_seed  # (dens imports this module)
+        """the word of the next step goes out"""
         v = step_seed(self.seed or 0, self.k)
         self.k += 1
-        self.host[0] = v - (1 << 64) if v >= (1 << 63) else v  # the same 64 bits inside int64's signed range
-        self.dev.copy_(self.host, non_blocking=True)
+        self.write(v - (1 << 64) if v >= (1 << 63) else v)  # the same 64 bits inside int64's signed range
 
     def scope(self):
         return droppath.device_draws(self.dev, base=0 if self.seed is not None else self.base)
@@ -88,7 +114,70 @@ def _scope(word):
     return word.scope() if word is not None else contextlib.nullcontext()
 
 
-class CapturedTrainStep:
+def _refuse_reducer(optimizer, name):
+    if getattr(optimizer, "_reducer", None) is not None:
+        raise ValueError("%s: data-parallel steps stay eager (the reducer's collectives are not captured)" % name)
+
+
+class _CapturingStep:
+    """The capture protocol of the step classes, written once.  A train step has `opt` (a FlatAdamW, whose device words and
+    step count the protocol looks after) and `_seed` (the _DeviceWord of the attention dropout's seed offset); an evaluation
+    step has neither, and the optimizer's share of the protocol is left out."""
+
+    opt = _seed = None
+
+    def _capture(self, run, store, **kept):
+        """Record run() in a HIP graph, hand the record -- dict(graph=the CUDAGraph, out=what run returned, **kept) -- to `store`,
+        which files it, and replay the graph once: capturing enqueued nothing.  The launches record the addresses of the
+        EdgeGraph's tensors, of the inputs run() reads and of the gradients / activations / outputs the graph's private pool
+        hands out.  Returns what run returned."""
+        train = self.opt is not None
+        if train:
+            self.opt.device_hyper(True)
+        graph = torch.cuda.CUDAGraph()
+        with ops.dropout_seed_offset(self._seed.dev) if train else contextlib.nullcontext(), ops._arena.capture_scope():
+            step_before = self.opt._step if train else None
+            with torch.cuda.graph(graph):
+                out = run()
+            if train:
+                self.opt._step = step_before  # (the step count advances with the replays)
+        store(dict(graph=graph, out=out, **kept))
+        if train:
+            _draw_seed(self._seed)
+        self._replay(graph)
+        return out
+
+    def _replay(self, graph):
+        if self.opt is not None:
+            self.opt.advance_captured()
+        graph.replay()
+        self.replays += 1
+
+
+class _TrainStep(_CapturingStep):
+    """What the two train steps are made of: optimizer, forward_loss, the two device words and the eager step."""
+
+    _drop_path = None  # the _DropPathWord the constructor makes (an instance built without it draws on the host, as before)
+
+    def _init_train(self, optimizer, forward_loss, drop_path_seed):
+        self.opt, self.forward_loss = optimizer, forward_loss
+        dev = optimizer.flat_p.device
+        self._seed = _DeviceWord(dev)
+        self._drop_path = _DropPathWord(drop_path_seed, dev)
+
+    def _run(self, g, *view):
+        """one eager step (also what a captured graph records)"""
+        with _scope(self._drop_path):  # (eager steps and the capture alike: one sequence of stochastic-depth masks)
+            self.opt.zero_grad(set_to_none=True)
+            loss = self.forward_loss(g, *view)
+            loss.backward()
+            self.opt.step()
+        # detached: a caller that keeps the loss of an EAGER step must not keep that step's autograd graph alive into a later
+        # capture (hipStreamEndCapture crashed with one alive, round 6)
+        return loss.detach()
+
+
+class CapturedTrainStep(_TrainStep):
     """cs = CapturedTrainStep(model_params_owner_optimizer, forward_loss)
        loss = cs.step(build_graph)          # every train step
 
@@ -99,77 +188,38 @@ class CapturedTrainStep:
     optimizer: a FlatAdamW without a reducer.  drop_path_seed: the seed of stochastic depth and of the equivariant dropouts
     (module docstring; None: drawn)."""
 
-    _drop_path = None  # the _DropPathWord the constructor makes (an instance built without it draws on the host, as before)
-
     def __init__(self, optimizer, forward_loss, min_eager=3, max_graphs=4, drop_path_seed=None):
-        if getattr(optimizer, "_reducer", None) is not None:
-            raise ValueError("CapturedTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
-        self.opt, self.forward_loss = optimizer, forward_loss
+        _refuse_reducer(optimizer, "CapturedTrainStep")
+        self._init_train(optimizer, forward_loss, drop_path_seed)
         self.min_eager, self.max_graphs = int(min_eager), int(max_graphs)
-        self._graphs = {}   # (N, E) -> dict(graph=CUDAGraph, sg=EdgeGraph, loss=Tensor)
+        self._graphs = {}   # (N, E) -> dict(graph=CUDAGraph, out=the loss, sg=EdgeGraph)
         self._seen = {}     # (N, E) -> eager steps so far (counts only: an EdgeGraph kept here would never be freed)
-        dev = optimizer.flat_p.device
-        self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-        self._drop_path = _DropPathWord(drop_path_seed, dev)
         self.replays = self.eager_steps = 0
-
-    # ---- one eager step (also what a captured graph records) -------------------------------------------------------
-    def _run(self, g):
-        with _scope(self._drop_path):  # (eager steps and the capture alike: one sequence of stochastic-depth masks)
-            self.opt.zero_grad(set_to_none=True)
-            loss = self.forward_loss(g)
-            loss.backward()
-            self.opt.step()
-        # detached: a caller that keeps the loss of an EAGER step must not keep that step's autograd graph alive into a later
-        # capture (hipStreamEndCapture crashed with one alive, round 6)
-        return loss.detach()
-
-    def _draw_seed(self):
-        self._seed_host[0] = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator, as the eager layers draw theirs
-        self._seed_dev.copy_(self._seed_host, non_blocking=True)
 
     def step(self, build_graph):
         _advance(self._drop_path)
         # the radius graph of this batch: into the tensors of a captured shape when one fits (tried most recent first)
         g = None
         for key, rec in reversed(list(self._graphs.items())):
-            if not getattr(rec["sg"], "_radius_static", False):  # (abandoned by a build that found another edge count)
+            if not rec["sg"]._radius_static:  # (abandoned by a build that found another edge count)
                 del self._graphs[key]
                 continue
-            self._draw_seed()  # (the device words go out BEFORE the graph build's host read-back: they overlap it)
+            _draw_seed(self._seed)  # (the device words go out BEFORE the graph build's host read-back: they overlap it)
             g = build_graph(rec["sg"])
             if g is rec["sg"]:
-                self.opt.advance_captured()
-                rec["graph"].replay()
-                self.replays += 1
-                return rec["loss"]
+                self._replay(rec["graph"])
+                return rec["out"]
             del self._graphs[key]  # its tensors were overwritten by the build of another shape: the graph is gone
             break  # (one rebuild attempt per step: a second one would repeat the neighbour search)
         if g is None:
             g = build_graph(None)
         key = (g.N, g.E)
         n = self._seen.get(key, 0)
-        if n < self.min_eager or len(self._graphs) >= self.max_graphs or not getattr(g, "_radius_static", False):
+        if n < self.min_eager or len(self._graphs) >= self.max_graphs or not g._radius_static:
             self._seen[key] = n + 1
             self.eager_steps += 1
             return self._run(g)
-        # capture this shape: the launches record the addresses of g's tensors, of the inputs forward_loss reads and of the
-        # gradients / activations the graph's private pool hands out
-        self.opt.device_hyper(True)
-        graph = torch.cuda.CUDAGraph()
-        with ops.dropout_seed_offset(self._seed_dev), ops._arena.capture_scope():
-            step_before = self.opt._step
-            with torch.cuda.graph(graph):
-                loss = self._run(g)
-            self.opt._step = step_before  # (capturing enqueued nothing: the step count advances with the replays)
-        rec = dict(graph=graph, sg=g, loss=loss)
-        self._graphs[key] = rec
-        self._draw_seed()
-        self.opt.advance_captured()
-        graph.replay()
-        self.replays += 1
-        return loss
+        return self._capture(lambda: self._run(g), functools.partial(self._graphs.__setitem__, key), sg=g)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -184,7 +234,6 @@ def bucket_of(B, N, E, node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP)
     edge_step - 1 phantom edges; N_cap: N plus the phantom nodes that many edges can need (`min_phantom_nodes(edge_step - 1)`,
     reserved whatever E is, so that the bucket depends on N and E separately), rounded up to a multiple of node_step.  A pure
     host function of its arguments."""
-    from .graph import min_phantom_nodes
     node_step, edge_step = int(node_step), int(edge_step)
     if node_step < 1 or edge_step < 1:
         raise ValueError("bucket steps must be positive")
@@ -195,7 +244,6 @@ def bucket_of(B, N, E, node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP)
 
 def bucket_corner(key, node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP):
     """The largest real (N, E) that `bucket_of` maps to the bucket `key`."""
-    from .graph import min_phantom_nodes
     return key[1] - min_phantom_nodes(int(edge_step) - 1), key[2]
 
 
@@ -224,14 +272,15 @@ class PaddedBatch:
     `model(view, graph=graph, offsets=view.offsets)` with "tags" among the node targets."""
 
 
-class _BucketedStep:
+class _BucketedStep(_CapturingStep):
     """What BucketedTrainStep and equiformer_amd.evaluate.BucketedEvalStep share: the bucket records with their LRU order and
-    counters, the padded view of a bucket's graph, its target buffers, and the first half of a step (the plan of the batch's
-    radius graph -- the one host read-back -- and its bucket key)."""
+    counters, the padded view of a bucket's graph, its target buffers, the plan of the batch's graph (the one host read-back) with
+    its bucket key, and `step` itself.  A subclass supplies `_run(g, view)` (one eager step, also what a capture records) and,
+    where it has any, `_check` (its pre-checks), `_words_out` (the device words of the step) and `_returned` (how the outputs
+    of a run or of a record are handed to the caller)."""
 
     def _init_buckets(self, radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors,
                       edges="search"):
-        import collections
         if edges not in ("search", "batch"):
             raise ValueError("edges must be \"search\" (neighbours found on the GPU) or \"batch\" (the batch's own edge list), got %r"
                              % (edges,))
@@ -255,7 +304,7 @@ class _BucketedStep:
         # (detached aliases: a model that marks `pos` as requiring grad -- the MD17 force pass -- must not mark the graph's buffer)
         v.pos, v.z, v.batch = g.pos.detach(), g.z, g.batch
         v.node_mask, v.graph_mask, v.B = g.node_mask, g.graph_mask, B
-        if getattr(g, "_pbc", False):
+        if g._pbc:
             v.offsets, v.cell_offsets, v.atomic_numbers = g.offsets, g.cell_offsets, g.z
         return v
 
@@ -275,7 +324,6 @@ class _BucketedStep:
 
     def _plan(self, batch):
         """(B, z, plan, build, key) of a batch: the graph plan (its host read-back happens here) and the bucket it falls into"""
-        from .graph import EdgeGraph
         b = batch["batch"]
         B = int(batch["num_graphs"]) if "num_graphs" in batch else int(b[-1].item()) + 1
         z = batch["z"] if "z" in batch else batch.get("atomic_numbers")
@@ -328,8 +376,39 @@ class _BucketedStep:
         self.captures += 1
         self.captures_of[key] = self.captures_of.get(key, 0) + 1
 
+    def _check(self, batch):
+        self._check_periodic(batch)
 
-class BucketedTrainStep(_BucketedStep):
+    def _words_out(self):
+        pass
+
+    def _returned(self, out, B, n_real):
+        return out
+
+    def step(self, batch):
+        self._check(batch)  # (before the batch is touched)
+        self._words_out()   # (the device words go out BEFORE the graph build's host read-back: they overlap it)
+        B, z, plan, build, key = self._plan(batch)
+        rec = self._graphs.get(key)
+        if rec is not None:
+            self._graphs.move_to_end(key)
+            build(plan, key[1:], into=rec["sg"], z=z)
+            self._fill_targets(rec["view"], batch, rec["sg"], B, fresh=False)
+            self._replay(rec["graph"])
+            return self._returned(rec["out"], B, plan.N)
+        g = build(plan, key[1:], z=z)
+        view = self._view(g, B)
+        self._fill_targets(view, batch, g, B, fresh=True)
+        if self._count_eager(key):
+            return self._returned(self._run(g, view), B, plan.N)
+        self._make_room()
+        # capture this bucket: beside what every capture records (_capture), the launches hold the addresses of the view's
+        # buffers; they see N_cap, E_cap and B + 1 only
+        out = self._capture(lambda: self._run(g, view), functools.partial(self._captured, key), sg=g, view=view)
+        return self._returned(out, B, plan.N)
+
+
+class BucketedTrainStep(_TrainStep, _BucketedStep):
     """bs = BucketedTrainStep(optimizer, forward_loss, radius, graph_targets=("y",), node_targets=())
        loss = bs.step(batch)        # batch: mapping with pos [N, 3], z [N], batch [N] (ascending) and the targets; N, E vary
 
@@ -355,65 +434,21 @@ class BucketedTrainStep(_BucketedStep):
     of a bucket) run on the same padded inputs as the replays.  Dropout seed word, stochastic-depth seed word (`drop_path_seed`)
     and AdamW device words as CapturedTrainStep; a reducer is refused likewise."""
 
-    _drop_path = None  # (see CapturedTrainStep)
-
     def __init__(self, optimizer, forward_loss, radius, graph_targets=("y",), node_targets=(), min_eager=3, max_graphs=16,
                  node_step=DEFAULT_NODE_STEP, edge_step=DEFAULT_EDGE_STEP, max_num_neighbors=1000, drop_path_seed=None,
                  edges="search"):
-        if getattr(optimizer, "_reducer", None) is not None:
-            raise ValueError("BucketedTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
-        self.opt, self.forward_loss = optimizer, forward_loss
+        _refuse_reducer(optimizer, "BucketedTrainStep")
         self._init_buckets(radius, graph_targets, node_targets, min_eager, max_graphs, node_step, edge_step, max_num_neighbors,
                            edges)
-        dev = optimizer.flat_p.device
-        self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-        self._drop_path = _DropPathWord(drop_path_seed, dev)
+        self._init_train(optimizer, forward_loss, drop_path_seed)
 
-    def _run(self, g, view):
-        with _scope(self._drop_path):  # (see CapturedTrainStep._run)
-            self.opt.zero_grad(set_to_none=True)
-            loss = self.forward_loss(g, view)
-            loss.backward()
-            self.opt.step()
-        return loss.detach()  # (see CapturedTrainStep._run)
-
-    def _draw_seed(self):
-        self._seed_host[0] = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self._seed_dev.copy_(self._seed_host, non_blocking=True)
-
-    def step(self, batch):
-        self._check_periodic(batch)
-        self._draw_seed()  # (the device words go out BEFORE the graph build's host read-back: they overlap it)
+    def _words_out(self):
+        _draw_seed(self._seed)
         _advance(self._drop_path)
-        B, z, plan, build, key = self._plan(batch)
-        rec = self._graphs.get(key)
-        if rec is not None:
-            self._graphs.move_to_end(key)
-            build(plan, key[1:], into=rec["sg"], z=z)
-            self._fill_targets(rec["view"], batch, rec["sg"], B, fresh=False)
-            self.opt.advance_captured()
-            rec["graph"].replay()
-            self.replays += 1
-            return rec["loss"]
-        g = build(plan, key[1:], z=z)
-        view = self._view(g, B)
-        self._fill_targets(view, batch, g, B, fresh=True)
-        if self._count_eager(key):
-            return self._run(g, view)
-        self._make_room()
-        # capture this bucket: the launches record the addresses of g's tensors, of the view's buffers and of the gradients /
-        # activations the graph's private pool hands out; they see N_cap, E_cap and B + 1 only
-        self.opt.device_hyper(True)
-        graph = torch.cuda.CUDAGraph()
-        with ops.dropout_seed_offset(self._seed_dev), ops._arena.capture_scope():
-            step_before = self.opt._step
-            with torch.cuda.graph(graph):
-                loss = self._run(g, view)
-            self.opt._step = step_before  # (capturing enqueued nothing: the step count advances with the replays)
-        self._captured(key, dict(graph=graph, sg=g, view=view, loss=loss))
-        self._draw_seed()
-        self.opt.advance_captured()
-        graph.replay()
-        self.replays += 1
-        return loss
+
+
+class _MirrorsBucketed:
+    """the counters of the BucketedTrainStep a task step (dens.py, is2rs.py) wraps as `.bucketed`"""
+    eager_steps = property(lambda self: self.bucketed.eager_steps)
+    captures = property(lambda self: self.bucketed.captures)
+    replays = property(lambda self: self.bucketed.replays)

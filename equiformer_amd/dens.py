@@ -16,16 +16,10 @@ What runs where in a step of `DeNSTrainStep`:
 import torch
 
 from . import ops
-from .capture import BucketedTrainStep
+from .capture import BucketedTrainStep, _MirrorsBucketed, _refuse_reducer
+from .droppath import step_seed  # noqa: F401  (re-exported: the corruption seed of step k)
 
-_MASK64 = 2 ** 64 - 1
 STATS = ("loss_e", "loss_f", "loss_d", "n_f", "n_d", "mae_e", "mae_f", "mae_d")  # DeNSLoss.stats, in this order
-
-
-def step_seed(seed, k):
-    """The corruption seed of step k (0-based) of a run seeded with `seed`: (seed + k * 0x9E3779B97F4A7C15) mod 2^64.  The
-    kernel hashes the seed, so consecutive values give unrelated draws."""
-    return (int(seed) + int(k) * 0x9E3779B97F4A7C15) & _MASK64
 
 
 def add_masked_gaussian_noise_to_pos(data, std, prob, corrupt_ratio=None, seed=None):
@@ -83,7 +77,7 @@ class DeNSLoss:
                              self.task_std, self.denoising_pos_std, row_mask=row_mask, stats_out=self.stats)
 
 
-class DeNSTrainStep:
+class DeNSTrainStep(_MirrorsBucketed):
     """ts = DeNSTrainStep(model, optimizer, loss, radius, std, prob, corrupt_ratio=None, seed=0, **bucket_kwargs)
        l = ts.step(batch)       # batch: mapping with pos [N, 3], z [N], batch [N] (ascending), y [B], dy [N, 3][, num_graphs]
 
@@ -99,8 +93,7 @@ class DeNSTrainStep:
     NODE_TARGETS = ("dy", "force", "noise_vec", "noise_mask")
 
     def __init__(self, model, optimizer, loss, radius, std, prob, corrupt_ratio=None, seed=0, **bucket_kwargs):
-        if getattr(optimizer, "_reducer", None) is not None:
-            raise ValueError("DeNSTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
+        _refuse_reducer(optimizer, "DeNSTrainStep")
         self.model, self.loss = model, loss
         self.std, self.prob, self.corrupt_ratio, self.seed = float(std), float(prob), corrupt_ratio, int(seed)
         self.steps = 0
@@ -111,10 +104,6 @@ class DeNSTrainStep:
     def _forward_loss(self, g, view):
         E, dy_pred = self.model(view, graph=g)
         return self.loss(E[:view.B], dy_pred, view, row_mask=view.node_mask, num_graphs=view.B)
-
-    eager_steps = property(lambda self: self.bucketed.eager_steps)
-    captures = property(lambda self: self.bucketed.captures)
-    replays = property(lambda self: self.bucketed.replays)
 
     def step(self, batch):
         b = batch["batch"]

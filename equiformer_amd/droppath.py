@@ -33,6 +33,13 @@ def mix64(z):
     return z ^ (z >> 31)
 
 
+def step_seed(seed, k):
+    """The seed of step k (0-based) of a run seeded with `seed`: (seed + k * 0x9E3779B97F4A7C15) mod 2^64 -- of the corruption
+    (dens.py), of the perturbation (is2rs.py), of stochastic depth and the equivariant dropouts (capture.py).  The kernels
+    hash the seed, so consecutive values give unrelated draws."""
+    return (int(seed) + int(k) * 0x9E3779B97F4A7C15) & _MASK64
+
+
 def rand_bits(seed, tag, idx):
     """eqf_rand_bits: the 64 bits of draw `idx` of stream `tag`"""
     key = mix64(int(seed) + 0xD6E8FEB86659FD93 * (int(tag) + 1))

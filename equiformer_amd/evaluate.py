@@ -137,7 +137,7 @@ class BucketedEvalStep(_BucketedStep):
     Per bucket one HIP graph holds predict + the update; buckets, `min_eager`, `max_graphs` (least recently used evicted) and
     the counters are those of BucketedTrainStep.  predict runs under no_grad; a model that needs its own autograd pass (the
     MD17 and DeNS models take a first-order force pass in eval mode) enables grad itself.  The outputs are detached inside the
-    recorded region, so no autograd graph is alive when the capture ends (see CapturedTrainStep._run).
+    recorded region, so no autograd graph is alive when the capture ends (see capture._TrainStep._run).
 
     `step` returns the REAL rows (energy[:B], forces[:n_real] or None) as views of the bucket's static buffers: valid until the
     next step of that bucket.  model: the module(s) predict calls; a step with one of them (or of the modules found on
@@ -173,40 +173,17 @@ class BucketedEvalStep(_BucketedStep):
                                   view.dy if with_forces else None, view.node_mask if with_forces else None)
         return energy, forces
 
-    @staticmethod
-    def _real(energy, forces, B, n_real):
-        return energy[:B], None if forces is None else forces[:n_real]
-
-    def step(self, batch):
+    def _check(self, batch):
         self._check_eval()
         self._check_periodic(batch)
         if self.device is not None and batch["pos"].device != self.device:
             raise ValueError("BucketedEvalStep: the batch is on %s, the step on %s" % (batch["pos"].device, self.device))
-        B, z, plan, build, key = self._plan(batch)
-        rec = self._graphs.get(key)
-        if rec is not None:
-            self._graphs.move_to_end(key)
-            build(plan, key[1:], into=rec["sg"], z=z)
-            self._fill_targets(rec["view"], batch, rec["sg"], B, fresh=False)
-            rec["graph"].replay()
-            self.replays += 1
-            return self._real(rec["energy"], rec["forces"], B, plan.N)
-        g = build(plan, key[1:], z=z)
-        view = self._view(g, B)
-        self._fill_targets(view, batch, g, B, fresh=True)
-        if self._count_eager(key):
-            return self._real(*self._run(g, view), B, plan.N)
-        self._make_room()
-        # capture this bucket: the launches record the addresses of g's tensors, of the view's buffers, of the parameters, of the
-        # meter's sums and of the outputs the graph's private pool hands out; they see N_cap, E_cap and B + 1 only
-        graph = torch.cuda.CUDAGraph()
-        with ops._arena.capture_scope():
-            with torch.cuda.graph(graph):
-                energy, forces = self._run(g, view)
-        self._captured(key, dict(graph=graph, sg=g, view=view, energy=energy, forces=forces))
-        graph.replay()  # (capturing enqueued nothing: neither the outputs nor the meter have seen this batch yet)
-        self.replays += 1
-        return self._real(energy, forces, B, plan.N)
+
+    def _returned(self, out, B, n_real):
+        """the real rows (a capture also holds the addresses of the parameters and of the meter's sums; its first replay is
+        what shows this batch to the outputs and the meter)"""
+        energy, forces = out
+        return energy[:B], None if forces is None else forces[:n_real]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the three loops

@@ -4,7 +4,13 @@ The reference builds `edge_index` with torch_cluster.radius_graph (nets/graph_at
 scatters with atomics; here the graph is produced already grouped by destination node (the order torch_cluster
 emits as well), together with the CSR offsets and the by-source permutation that turn every scatter / gather
 backward into an atomics-free segmented reduction.
+
+Three edge sources -- the neighbour search, the periodic neighbour search, a GIVEN periodic edge list -- go through one
+pipeline: a plan (`radius_plan`, `radius_pbc_plan`, `edges_pbc_plan`: counts, scans, the one host read-back), then the graph of
+the plan, exact-shape (`_build_exact`) or padded to a capacity (`_build_padded`).  A source contributes its fill kernel, the
+per-edge tensors it owns and its by-source entry point (`_Source`); everything else is written once.
 """
+import collections
 import ctypes
 
 import torch
@@ -76,8 +82,29 @@ class EdgesPbcPlan:
                  "edge_index", "cell_offsets", "index64", "offsets64", "keep", "off")
 
 
+# What an edge source contributes to the second half of a build.  fill(plan, g): the plan's E real edges into the head of g's
+# per-edge tensors; per_edge: (name, trailing shape, dtype, value of a phantom edge's row) of the per-edge tensors it owns beside
+# src / dst; by_source: the entry point of its by-source view; pbc / given: the flags its graphs carry (`_pbc`; `order` present);
+# own_rows: an exact-shape graph keeps copies of the plan's row_ptr / batch / mol_ptr, not the plan's tensors themselves;
+# too_large: the refusal of a padded graph with more than CSR_MAX_NODES nodes in a molecule.
+_Source = collections.namedtuple("_Source", "fill per_edge by_source pbc given own_rows too_large")
+
+
+def _sorted_by_source(src, N):
+    """(src_perm, src_ptr) of an arbitrary edge list (it may repeat a source inside a row and need not be structure-blocked):
+    stable device sort"""
+    order = torch.argsort(src.to(torch.int64), stable=True)
+    return _i32(order), _ptr_from_counts(torch.bincount(src.to(torch.int64), minlength=N))
+
+
 class EdgeGraph:
     """N nodes, E directed edges sorted by dst.  All index tensors are int32 on the GPU."""
+
+    # optional state, set by the builder that owns it.  _padded: padded to `capacity` with one phantom molecule; _pbc: periodic
+    # (owns `offsets` / `cell_offsets`); _radius_static: every tensor is refilled in place by enqueue-only kernels (what a captured
+    # step needs; a build that finds other counts clears it: abandoned); order: the input slot of each edge of a GIVEN edge list.
+    _padded = _pbc = _radius_static = False
+    z = order = offsets = cell_offsets = capacity = None
 
     def __init__(self, N, src, dst, row_ptr, batch=None, num_graphs=None, mol_ptr=None, max_mol_nodes=None, by_source_into=None):
         self.N = int(N)
@@ -94,10 +121,7 @@ class EdgeGraph:
             call("eqf_csr_by_source", _P(src), _P(row_ptr), _P(mol_ptr), int(mol_ptr.shape[0]) - 1, int(max_mol_nodes),
                  _P(self.src_perm), _P(self.src_ptr), _stream())
         else:
-            # arbitrary edge lists (they may repeat a source inside a row and need not be structure-blocked): stable device sort
-            order = torch.argsort(src.to(torch.int64), stable=True)
-            self.src_perm = _i32(order)
-            self.src_ptr = _ptr_from_counts(torch.bincount(src.to(torch.int64), minlength=self.N))
+            self.src_perm, self.src_ptr = _sorted_by_source(src, self.N)
         self.batch = None
         if batch is not None:
             self.set_batch(batch, num_graphs)
@@ -109,6 +133,114 @@ class EdgeGraph:
         self.num_graphs = int(num_graphs)
         self.mol_ptr = _ptr_from_counts(torch.bincount(batch.to(torch.int64), minlength=self.num_graphs))
 
+    # ---- the second half of every build: the graph of a plan, exact-shape or padded --------------------------------------------
+    @staticmethod
+    def _new(source, N, E, num_graphs, dev, by_source=True):
+        """a graph of `source`: src / dst, the per-edge tensors of the source and the by-source view allocated, nothing filled"""
+        g = EdgeGraph.__new__(EdgeGraph)
+        i32 = dict(dtype=torch.int32, device=dev)
+        g.N, g.E, g.num_graphs = N, E, num_graphs
+        g.src, g.dst = torch.empty(E, **i32), torch.empty(E, **i32)
+        if by_source:
+            g.src_perm, g.src_ptr = torch.empty(E, **i32), torch.empty(N + 1, **i32)
+        for name, shape, dtype, _ in source.per_edge:
+            setattr(g, name, torch.empty((E,) + shape, dtype=dtype, device=dev))
+        g._pbc = source.pbc
+        return g
+
+    @staticmethod
+    def _of_source(source, g):
+        """g is a graph that `source` built and that is still refillable in place"""
+        return (g is not None and g._radius_static and g._pbc == source.pbc and (g.order is not None) == source.given)
+
+    @staticmethod
+    def _build_exact(source, plan, into):
+        """The exact-shape graph of `plan`.  into: an exact-shape graph of this source; with the plan's node, structure and edge
+        counts every tensor of it is REWRITTEN in place and it is returned, otherwise the result is fresh and `into` is marked
+        as abandoned (its owner falls back to an eager step on the fresh graph: equiformer_amd/capture.py)."""
+        N, E, B = plan.N, plan.E, plan.num_graphs
+        dev = plan.pos.device
+        mol_ptr = plan.mol_ptr[:B + 1]
+        refill = EdgeGraph._of_source(source, into) and not into._padded
+        if refill and (into.N, into.E, into.num_graphs, into.src.device) != (N, E, B, dev):
+            into._radius_static = refill = False
+            if plan.row_ptr is into.row_ptr:  # (from_radius had the scan written straight into it)
+                plan.row_ptr = plan.row_ptr.clone()  # (the caller's tensors must not alias the abandoned graph's)
+        launch = refill or plan.max_mol_nodes <= CSR_MAX_NODES
+        if refill:
+            g = into
+        else:
+            g = EdgeGraph._new(source, N, E, B, dev, by_source=launch)
+            if source.own_rows:
+                i32 = dict(dtype=torch.int32, device=dev)
+                g.row_ptr, g.batch, g.mol_ptr = torch.empty(N + 1, **i32), torch.empty(N, **i32), torch.empty(B + 1, **i32)
+            else:
+                g.row_ptr, g.batch, g.mol_ptr = plan.row_ptr, plan.b32, mol_ptr
+        with torch.no_grad():
+            for mine, planned in ((g.row_ptr, plan.row_ptr), (g.mol_ptr, mol_ptr), (g.batch, plan.b32)):
+                if mine.data_ptr() != planned.data_ptr():
+                    mine.copy_(planned)
+        source.fill(plan, g)
+        if launch:
+            call(source.by_source, _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B, max(int(plan.max_mol_nodes), 1),
+                 _P(g.src_perm), _P(g.src_ptr), _stream())
+        else:  # (molecules beyond the cursor kernels' LDS)
+            g.src_perm, g.src_ptr = _sorted_by_source(g.src, N)
+        g._radius_static = launch  # (refillable in place: every tensor comes from an enqueue-only kernel)
+        return g
+
+    @staticmethod
+    def _build_padded(source, plan, capacity, into, z):
+        """The graph of `plan` padded to capacity = (N_cap, E_cap) with one phantom molecule (csrc/graph.hip eqf_graph_pad_tail):
+        what `from_radius_plan` documents, for every source.  Phantom edges get the source's phantom row in its per-edge tensors.
+        into: a padded graph of this source with the same capacity, molecule count and `z` presence, refilled in place and
+        returned.  Raises GraphDoesNotFit before anything of `into` is written."""
+        n_cap, e_cap = int(capacity[0]), int(capacity[1])
+        N, E, B = plan.N, plan.E, plan.num_graphs
+        P, Q = n_cap - N, e_cap - E
+        # (P < 0 needs no test of its own: min_phantom_nodes(Q) >= 0 > P then)
+        if Q < 0 or P < min_phantom_nodes(Q):
+            raise GraphDoesNotFit("%d nodes / %d edges do not fit the capacity (%d, %d): %d phantom edges need %d phantom nodes"
+                                  % (N, E, n_cap, e_cap, max(Q, 0), min_phantom_nodes(max(Q, 0))))
+        if max(plan.max_mol_nodes, P) > CSR_MAX_NODES:
+            raise ops.HipOnlyError(source.too_large % CSR_MAX_NODES)
+        dev = plan.pos.device
+        if (EdgeGraph._of_source(source, into) and into._padded and into.N == n_cap and into.E == e_cap
+                and into.num_graphs == B + 1 and into.src.device == dev and (into.z is None) == (z is None)):
+            g = into
+        else:
+            g = EdgeGraph._new(source, n_cap, e_cap, B + 1, dev)
+            i32 = dict(dtype=torch.int32, device=dev)
+            g.row_ptr, g.batch, g.mol_ptr = torch.empty(n_cap + 1, **i32), torch.empty(n_cap, **i32), torch.empty(B + 2, **i32)
+            g.pos = torch.empty((n_cap, 3), dtype=torch.float32, device=dev)
+            g.z = torch.empty(n_cap, dtype=torch.int64, device=dev) if z is not None else None
+            g.node_mask = torch.empty(n_cap, dtype=torch.float32, device=dev)
+            g.graph_mask = torch.empty(B + 1, dtype=torch.float32, device=dev)
+            g._padded = g._radius_static = True
+            g.capacity = (n_cap, e_cap)
+        g.n_real, g.e_real, g.num_real_graphs = N, E, B
+        with torch.no_grad():
+            g.row_ptr[:N + 1].copy_(plan.row_ptr)
+            g.mol_ptr[:B + 1].copy_(plan.mol_ptr[:B + 1])
+            g.batch[:N].copy_(plan.b32)
+            g.pos[:N].copy_(plan.pos)
+            if z is not None:
+                g.z[:N].copy_(z)
+            if Q:
+                for name, _, _, phantom in source.per_edge:
+                    if phantom:
+                        getattr(g, name)[E:].fill_(phantom)
+                    else:
+                        getattr(g, name)[E:].zero_()
+        source.fill(plan, g)
+        st = _stream()
+        call("eqf_graph_pad_tail", N, E, n_cap, e_cap, B, _P(g.row_ptr), _P(g.src), _P(g.dst), _P(g.batch), _P(g.mol_ptr),
+             _P(g.pos), _P(g.z), _P(g.node_mask), _P(g.graph_mask), st)
+        call(source.by_source, _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
+             _P(g.src_perm), _P(g.src_ptr), st)
+        return g
+
+    # ---- radius graph (csrc/graph.hip radius_graph_count / radius_graph_fill; by-source view: eqf_csr_by_source) ----------------
     @staticmethod
     def from_radius(pos, batch, r, max_num_neighbors=1000, num_graphs=None, into=None, capacity=None, z=None):
         """Radius graph per molecule (nodes of a molecule contiguous, `batch` ascending).  into: a graph of an earlier call; when
@@ -120,54 +252,20 @@ class EdgeGraph:
         if capacity is not None:
             plan = EdgeGraph.radius_plan(pos, batch, r, max_num_neighbors, num_graphs)
             return EdgeGraph.from_radius_plan(plan, capacity, into=into, z=z)
-        if not pos.is_cuda:
-            raise ops.HipOnlyError("radius graph construction runs on the GPU only")
-        pos = pos.detach().to(torch.float32).contiguous()
-        N = pos.shape[0]
         if num_graphs is None:
             num_graphs = int(batch[-1].item()) + 1
-        dev = pos.device
-        b32 = _i32(batch)
-        st = _stream()
-        stats = torch.empty(2, dtype=torch.int32, device=dev)  # [E, nodes of the largest molecule]
-        mol_ptr = torch.empty(num_graphs + 1, dtype=torch.int32, device=dev)
-        call("eqf_segment_ptr", _P(b32), N, int(num_graphs), _P(mol_ptr), _P(stats, 4), st)
-        deg = torch.empty(N, dtype=torch.int32, device=dev)
-        call("eqf_radius_graph_count", _P(pos), _P(mol_ptr), num_graphs, float(r), int(max_num_neighbors), _P(deg), st)
-        reuse = (into is not None and into.N == N and into.num_graphs == int(num_graphs) and into.src.device == dev
-                 and getattr(into, "_radius_static", False))
-        # (a candidate for in-place reuse gets the scan written straight into its row_ptr: if the edge count then differs the graph
-        # is abandoned by its owner anyway -- equiformer_amd/capture.py falls back to an eager step on a fresh graph)
-        row_ptr = into.row_ptr if reuse else torch.empty(N + 1, dtype=torch.int32, device=dev)
-        call("eqf_exclusive_scan_i32", _P(deg), N, _P(row_ptr), _P(stats), st)
-        E, max_mol_nodes = stats.tolist()  # the one host sync of graph construction (the reference syncs here as well)
-        if reuse and into.E != E:
-            row_ptr = row_ptr.clone()  # (the caller's tensors must not alias the abandoned graph's)
-            into._radius_static = False
-        if reuse and into.E == E:
-            into.mol_ptr.copy_(mol_ptr)
-            if into.batch.data_ptr() != b32.data_ptr():
-                into.batch.copy_(b32)
-            call("eqf_radius_graph_fill", _P(pos), _P(into.mol_ptr), num_graphs, float(r), int(max_num_neighbors),
-                 _P(into.row_ptr), _P(into.src), _P(into.dst), st)
-            call("eqf_csr_by_source", _P(into.src), _P(into.row_ptr), _P(into.mol_ptr), int(num_graphs), int(max_mol_nodes),
-                 _P(into.src_perm), _P(into.src_ptr), st)
-            return into
-        src = torch.empty(E, dtype=torch.int32, device=dev)
-        dst = torch.empty(E, dtype=torch.int32, device=dev)
-        call("eqf_radius_graph_fill", _P(pos), _P(mol_ptr), num_graphs, float(r), int(max_num_neighbors), _P(row_ptr),
-             _P(src), _P(dst), st)
-        g = EdgeGraph(N, src, dst, row_ptr, mol_ptr=mol_ptr, max_mol_nodes=max_mol_nodes)
-        g._radius_static = max_mol_nodes <= CSR_MAX_NODES  # (its by-source view came from eqf_csr_by_source: refillable in place)
-        g.batch = b32
-        g.num_graphs = int(num_graphs)
-        g.mol_ptr = mol_ptr
-        return g
+        # a candidate for in-place reuse gets the scan written straight into its row_ptr: if the edge count then differs the graph
+        # is abandoned by its owner anyway -- equiformer_amd/capture.py falls back to an eager step on a fresh graph
+        if not (EdgeGraph._of_source(_SEARCH, into) and not into._padded
+                and (into.N, into.num_graphs, into.src.device) == (pos.shape[0], int(num_graphs), pos.device)):
+            into = None
+        plan = EdgeGraph.radius_plan(pos, batch, r, max_num_neighbors, num_graphs, row_ptr=None if into is None else into.row_ptr)
+        return EdgeGraph._build_exact(_SEARCH, plan, into)
 
-    # ---- radius graph padded to a capacity (one phantom molecule: csrc/graph.hip eqf_graph_pad_tail) ------------------------
     @staticmethod
-    def radius_plan(pos, batch, r, max_num_neighbors=1000, num_graphs=None):
-        """Degrees + scan + the one host read-back of a radius graph build; nothing of an earlier graph is touched."""
+    def radius_plan(pos, batch, r, max_num_neighbors=1000, num_graphs=None, row_ptr=None):
+        """Degrees + scan + the one host read-back of a radius graph build.  row_ptr: where the scan goes (`from_radius`: the
+        row_ptr of the graph it may refill); by default a new tensor, and nothing of an earlier graph is touched."""
         if not pos.is_cuda:
             raise ops.HipOnlyError("radius graph construction runs on the GPU only")
         p = RadiusPlan()
@@ -183,10 +281,18 @@ class EdgeGraph:
         call("eqf_segment_ptr", _P(p.b32), p.N, p.num_graphs, _P(p.mol_ptr), _P(stats, 4), st)
         deg = torch.empty(p.N, dtype=torch.int32, device=dev)
         call("eqf_radius_graph_count", _P(p.pos), _P(p.mol_ptr), p.num_graphs, p.r, p.max_num_neighbors, _P(deg), st)
-        p.row_ptr = torch.empty(p.N + 1, dtype=torch.int32, device=dev)
+        p.row_ptr = torch.empty(p.N + 1, dtype=torch.int32, device=dev) if row_ptr is None else row_ptr
         call("eqf_exclusive_scan_i32", _P(deg), p.N, _P(p.row_ptr), _P(stats), st)
-        p.E, p.max_mol_nodes = stats.tolist()  # the one host sync of graph construction
+        p.E, p.max_mol_nodes = stats.tolist()  # the one host sync of graph construction (the reference syncs here as well)
         return p
+
+    @staticmethod
+    def _radius_fill(plan, g):
+        """The E real edges of `plan` into the head of g.src / g.dst.  (An exact-shape graph's own mol_ptr / row_ptr are the
+        plan's or equal them; a padded graph's have the phantom molecule behind the real rows, which the kernel must not see.)"""
+        rows = plan if g._padded else g
+        call("eqf_radius_graph_fill", _P(plan.pos), _P(rows.mol_ptr), plan.num_graphs, plan.r, plan.max_num_neighbors,
+             _P(rows.row_ptr), _P(g.src), _P(g.dst), _stream())
 
     @staticmethod
     def from_radius_plan(plan, capacity, into=None, z=None):
@@ -197,48 +303,7 @@ class EdgeGraph:
         `graph_mask` [B + 1] (1 real, 0 phantom); `n_real`, `e_real`, `num_real_graphs` hold the real counts (host integers:
         never use them inside a captured step).  into: a padded graph of the same capacity and molecule count, refilled in
         place and returned.  Raises GraphDoesNotFit before anything of `into` is written."""
-        n_cap, e_cap = int(capacity[0]), int(capacity[1])
-        N, E, B = plan.N, plan.E, plan.num_graphs
-        P, Q = n_cap - N, e_cap - E
-        if Q < 0 or P < min_phantom_nodes(Q):
-            raise GraphDoesNotFit("%d nodes / %d edges do not fit the capacity (%d, %d): %d phantom edges need %d phantom nodes"
-                                  % (N, E, n_cap, e_cap, max(Q, 0), min_phantom_nodes(max(Q, 0))))
-        if max(plan.max_mol_nodes, P) > CSR_MAX_NODES:
-            raise ops.HipOnlyError("padded radius graphs need molecules (the phantom one included) of at most %d nodes" % CSR_MAX_NODES)
-        dev = plan.pos.device
-        st = _stream()
-        reuse = (into is not None and getattr(into, "_padded", False) and into.N == n_cap and into.E == e_cap
-                 and into.num_graphs == B + 1 and into.src.device == dev and (into.z is None) == (z is None))
-        if reuse:
-            g = into
-        else:
-            g = EdgeGraph.__new__(EdgeGraph)
-            i32 = dict(dtype=torch.int32, device=dev)
-            g.N, g.E, g.num_graphs = n_cap, e_cap, B + 1
-            g.src, g.dst = torch.empty(e_cap, **i32), torch.empty(e_cap, **i32)
-            g.row_ptr, g.batch, g.mol_ptr = torch.empty(n_cap + 1, **i32), torch.empty(n_cap, **i32), torch.empty(B + 2, **i32)
-            g.src_perm, g.src_ptr = torch.empty(e_cap, **i32), torch.empty(n_cap + 1, **i32)
-            g.pos = torch.empty((n_cap, 3), dtype=torch.float32, device=dev)
-            g.z = torch.empty(n_cap, dtype=torch.int64, device=dev) if z is not None else None
-            g.node_mask = torch.empty(n_cap, dtype=torch.float32, device=dev)
-            g.graph_mask = torch.empty(B + 1, dtype=torch.float32, device=dev)
-            g._padded = g._radius_static = True
-            g.capacity = (n_cap, e_cap)
-        g.n_real, g.e_real, g.num_real_graphs = N, E, B
-        with torch.no_grad():
-            g.row_ptr[:N + 1].copy_(plan.row_ptr)
-            g.mol_ptr[:B + 1].copy_(plan.mol_ptr[:B + 1])
-            g.batch[:N].copy_(plan.b32)
-            g.pos[:N].copy_(plan.pos)
-            if z is not None:
-                g.z[:N].copy_(z)
-        call("eqf_radius_graph_fill", _P(plan.pos), _P(plan.mol_ptr), B, plan.r, plan.max_num_neighbors, _P(plan.row_ptr),
-             _P(g.src), _P(g.dst), st)
-        call("eqf_graph_pad_tail", N, E, n_cap, e_cap, B, _P(g.row_ptr), _P(g.src), _P(g.dst), _P(g.batch), _P(g.mol_ptr),
-             _P(g.pos), _P(g.z), _P(g.node_mask), _P(g.graph_mask), st)
-        call("eqf_csr_by_source", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
-             _P(g.src_perm), _P(g.src_ptr), st)
-        return g
+        return EdgeGraph._build_padded(_SEARCH, plan, capacity, into, z)
 
     # ---- periodic radius graph (csrc/graph.hip pbc_count / pbc_fill; by-source view: eqf_csr_by_source_multi) ------------------
     @staticmethod
@@ -271,12 +336,12 @@ class EdgeGraph:
         return p
 
     @staticmethod
-    def _pbc_fill(plan, src, dst, cell_offsets, offsets):
-        """The E real edges of `plan` into the head of the given tensors (row_ptr of the plan: real rows only)."""
+    def _pbc_fill(plan, g):
+        """The E real edges of `plan` into the head of g's per-edge tensors (row_ptr of the plan: real rows only)."""
         scratch = torch.empty(max(plan.C, 1), dtype=torch.float32, device=plan.pos.device)
         call("eqf_radius_graph_pbc_fill", _P(plan.pos), _P(plan.cell), _P(plan.mol_ptr), plan.num_graphs, plan.r,
-             plan.max_num_neighbors, _P(plan.row_ptr), _P(plan.cand_ptr), _P(scratch), _P(src), _P(dst), _P(cell_offsets),
-             _P(offsets), _stream())
+             plan.max_num_neighbors, _P(plan.row_ptr), _P(plan.cand_ptr), _P(scratch), _P(g.src), _P(g.dst), _P(g.cell_offsets),
+             _P(g.offsets), _stream())
 
     @staticmethod
     def from_radius_pbc(pos, cell, batch, r, max_num_neighbors=50, num_graphs=None, into=None, capacity=None, z=None):
@@ -292,48 +357,9 @@ class EdgeGraph:
         plan = EdgeGraph.radius_pbc_plan(pos, cell, batch, r, max_num_neighbors, num_graphs)
         if capacity is not None:
             g = EdgeGraph.from_radius_pbc_plan(plan, capacity, into=into, z=z)
-            return g, g.offsets, g.cell_offsets
-        N, E, B = plan.N, plan.E, plan.num_graphs
-        dev = plan.pos.device
-        mol_ptr = plan.mol_ptr[:B + 1]
-        cand = (into is not None and getattr(into, "_pbc", False) and not getattr(into, "_padded", False)
-                and getattr(into, "_radius_static", False))
-        if cand and (into.N, into.E, into.num_graphs, into.src.device) == (N, E, B, dev):
-            with torch.no_grad():
-                into.row_ptr.copy_(plan.row_ptr)
-                into.mol_ptr.copy_(mol_ptr)
-                if into.batch.data_ptr() != plan.b32.data_ptr():
-                    into.batch.copy_(plan.b32)
-            EdgeGraph._pbc_fill(plan, into.src, into.dst, into.cell_offsets, into.offsets)
-            call("eqf_csr_by_source_multi", _P(into.src), _P(into.row_ptr), _P(into.mol_ptr), B, int(plan.max_mol_nodes),
-                 _P(into.src_perm), _P(into.src_ptr), _stream())
-            return into, into.offsets, into.cell_offsets
-        if cand:
-            into._radius_static = False  # (abandoned: its owner falls back to an eager step on the fresh graph)
-        src = torch.empty(E, dtype=torch.int32, device=dev)
-        dst = torch.empty(E, dtype=torch.int32, device=dev)
-        cell_offsets = torch.empty((E, 3), dtype=torch.int32, device=dev)
-        offsets = torch.empty((E, 3), dtype=torch.float32, device=dev)
-        EdgeGraph._pbc_fill(plan, src, dst, cell_offsets, offsets)
-        if plan.max_mol_nodes <= CSR_MAX_NODES:
-            # a source occurs once per image in a row: the cursor kernel that ranks equal sources inside the row, no device sort
-            g = EdgeGraph.__new__(EdgeGraph)
-            g.N, g.E = N, E
-            g.src, g.dst, g.row_ptr = src, dst, plan.row_ptr
-            g.src_perm = torch.empty(E, dtype=torch.int32, device=dev)
-            g.src_ptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-            call("eqf_csr_by_source_multi", _P(src), _P(plan.row_ptr), _P(mol_ptr), B, int(plan.max_mol_nodes),
-                 _P(g.src_perm), _P(g.src_ptr), _stream())
-            g._radius_static = True  # (refillable in place: every tensor comes from an enqueue-only kernel)
         else:
-            g = EdgeGraph(N, src, dst, plan.row_ptr)  # (structures beyond the cursor kernel's LDS: stable device sort)
-            g._radius_static = False
-        g._pbc = True
-        g.batch = plan.b32
-        g.num_graphs = B
-        g.mol_ptr = mol_ptr
-        g.offsets, g.cell_offsets = offsets, cell_offsets
-        return g, offsets, cell_offsets
+            g = EdgeGraph._build_exact(_SEARCH_PBC, plan, into)
+        return g, g.offsets, g.cell_offsets
 
     @staticmethod
     def from_radius_pbc_plan(plan, capacity, into=None, z=None):
@@ -344,53 +370,7 @@ class EdgeGraph:
         phantom edges get zero rows in both (the phantom nodes sit on pairwise distinct lattice points: no zero-length edge).
         into: a padded periodic graph of the same capacity and structure count, refilled in place and returned.  Raises
         GraphDoesNotFit before anything of `into` is written."""
-        n_cap, e_cap = int(capacity[0]), int(capacity[1])
-        N, E, B = plan.N, plan.E, plan.num_graphs
-        P, Q = n_cap - N, e_cap - E
-        if P < 0 or Q < 0 or P < min_phantom_nodes(Q):
-            raise GraphDoesNotFit("%d nodes / %d edges do not fit the capacity (%d, %d): %d phantom edges need %d phantom nodes"
-                                  % (N, E, n_cap, e_cap, max(Q, 0), min_phantom_nodes(max(Q, 0))))
-        if max(plan.max_mol_nodes, P) > CSR_MAX_NODES:
-            raise ops.HipOnlyError("padded periodic graphs need structures (the phantom one included) of at most %d nodes"
-                                   % CSR_MAX_NODES)
-        dev = plan.pos.device
-        st = _stream()
-        reuse = (into is not None and getattr(into, "_padded", False) and getattr(into, "_pbc", False) and into.N == n_cap
-                 and into.E == e_cap and into.num_graphs == B + 1 and into.src.device == dev and (into.z is None) == (z is None))
-        if reuse:
-            g = into
-        else:
-            g = EdgeGraph.__new__(EdgeGraph)
-            i32 = dict(dtype=torch.int32, device=dev)
-            g.N, g.E, g.num_graphs = n_cap, e_cap, B + 1
-            g.src, g.dst = torch.empty(e_cap, **i32), torch.empty(e_cap, **i32)
-            g.row_ptr, g.batch, g.mol_ptr = torch.empty(n_cap + 1, **i32), torch.empty(n_cap, **i32), torch.empty(B + 2, **i32)
-            g.src_perm, g.src_ptr = torch.empty(e_cap, **i32), torch.empty(n_cap + 1, **i32)
-            g.cell_offsets = torch.empty((e_cap, 3), **i32)
-            g.offsets = torch.empty((e_cap, 3), dtype=torch.float32, device=dev)
-            g.pos = torch.empty((n_cap, 3), dtype=torch.float32, device=dev)
-            g.z = torch.empty(n_cap, dtype=torch.int64, device=dev) if z is not None else None
-            g.node_mask = torch.empty(n_cap, dtype=torch.float32, device=dev)
-            g.graph_mask = torch.empty(B + 1, dtype=torch.float32, device=dev)
-            g._padded = g._radius_static = g._pbc = True
-            g.capacity = (n_cap, e_cap)
-        g.n_real, g.e_real, g.num_real_graphs = N, E, B
-        with torch.no_grad():
-            g.row_ptr[:N + 1].copy_(plan.row_ptr)
-            g.mol_ptr[:B + 1].copy_(plan.mol_ptr[:B + 1])
-            g.batch[:N].copy_(plan.b32)
-            g.pos[:N].copy_(plan.pos)
-            if z is not None:
-                g.z[:N].copy_(z)
-            if Q:
-                g.offsets[E:].zero_()
-                g.cell_offsets[E:].zero_()
-        EdgeGraph._pbc_fill(plan, g.src, g.dst, g.cell_offsets, g.offsets)
-        call("eqf_graph_pad_tail", N, E, n_cap, e_cap, B, _P(g.row_ptr), _P(g.src), _P(g.dst), _P(g.batch), _P(g.mol_ptr),
-             _P(g.pos), _P(g.z), _P(g.node_mask), _P(g.graph_mask), st)
-        call("eqf_csr_by_source_multi", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
-             _P(g.src_perm), _P(g.src_ptr), st)
-        return g
+        return EdgeGraph._build_padded(_SEARCH_PBC, plan, capacity, into, z)
 
     # ---- a GIVEN periodic edge list (csrc/graph.hip eqf_edges_pbc_count / eqf_edges_pbc_fill; by-source view: eqf_csr_by_source_multi)
     @staticmethod
@@ -467,78 +447,9 @@ class EdgeGraph:
         inputs, masks and host integers; `_padded`); phantom edges get zero rows in `offsets` / `cell_offsets` and -1 in `order`;
         `into` is a padded graph of this builder with the same capacity and structure count.  Raises GraphDoesNotFit before
         anything of `into` is written."""
-        N, E, B = plan.N, plan.E, plan.num_graphs
-        dev = plan.pos.device
-        st = _stream()
-        i32 = dict(dtype=torch.int32, device=dev)
-        given = into is not None and getattr(into, "order", None) is not None and getattr(into, "_pbc", False)
         if capacity is None:
-            cand = given and not getattr(into, "_padded", False) and getattr(into, "_radius_static", False)
-            if cand and (into.N, into.E, into.num_graphs, into.src.device) == (N, E, B, dev):
-                g = into
-            else:
-                if cand:
-                    into._radius_static = False  # (abandoned: its owner falls back to an eager step on the fresh graph)
-                g = EdgeGraph.__new__(EdgeGraph)
-                g.N, g.E, g.num_graphs = N, E, B
-                g.src, g.dst, g.order = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
-                g.row_ptr, g.batch, g.mol_ptr = torch.empty(N + 1, **i32), torch.empty(N, **i32), torch.empty(B + 1, **i32)
-                g.src_perm, g.src_ptr = torch.empty(E, **i32), torch.empty(N + 1, **i32)
-                g.cell_offsets = torch.empty((E, 3), **i32)
-                g.offsets = torch.empty((E, 3), dtype=torch.float32, device=dev)
-                g._pbc = g._radius_static = True
-            with torch.no_grad():
-                g.row_ptr.copy_(plan.row_ptr)
-                g.mol_ptr.copy_(plan.mol_ptr[:B + 1])
-                g.batch.copy_(plan.b32)
-            EdgeGraph._edges_pbc_fill(plan, g)
-            call("eqf_csr_by_source_multi", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B, max(int(plan.max_mol_nodes), 1),
-                 _P(g.src_perm), _P(g.src_ptr), st)
-            return g
-        n_cap, e_cap = int(capacity[0]), int(capacity[1])
-        P, Q = n_cap - N, e_cap - E
-        if P < 0 or Q < 0 or P < min_phantom_nodes(Q):
-            raise GraphDoesNotFit("%d nodes / %d edges do not fit the capacity (%d, %d): %d phantom edges need %d phantom nodes"
-                                  % (N, E, n_cap, e_cap, max(Q, 0), min_phantom_nodes(max(Q, 0))))
-        if max(plan.max_mol_nodes, P) > CSR_MAX_NODES:
-            raise ops.HipOnlyError("padded periodic graphs need structures (the phantom one included) of at most %d nodes"
-                                   % CSR_MAX_NODES)
-        reuse = (given and getattr(into, "_padded", False) and into.N == n_cap and into.E == e_cap
-                 and into.num_graphs == B + 1 and into.src.device == dev and (into.z is None) == (z is None))
-        if reuse:
-            g = into
-        else:
-            g = EdgeGraph.__new__(EdgeGraph)
-            g.N, g.E, g.num_graphs = n_cap, e_cap, B + 1
-            g.src, g.dst, g.order = torch.empty(e_cap, **i32), torch.empty(e_cap, **i32), torch.empty(e_cap, **i32)
-            g.row_ptr, g.batch, g.mol_ptr = torch.empty(n_cap + 1, **i32), torch.empty(n_cap, **i32), torch.empty(B + 2, **i32)
-            g.src_perm, g.src_ptr = torch.empty(e_cap, **i32), torch.empty(n_cap + 1, **i32)
-            g.cell_offsets = torch.empty((e_cap, 3), **i32)
-            g.offsets = torch.empty((e_cap, 3), dtype=torch.float32, device=dev)
-            g.pos = torch.empty((n_cap, 3), dtype=torch.float32, device=dev)
-            g.z = torch.empty(n_cap, dtype=torch.int64, device=dev) if z is not None else None
-            g.node_mask = torch.empty(n_cap, dtype=torch.float32, device=dev)
-            g.graph_mask = torch.empty(B + 1, dtype=torch.float32, device=dev)
-            g._padded = g._radius_static = g._pbc = True
-            g.capacity = (n_cap, e_cap)
-        g.n_real, g.e_real, g.num_real_graphs = N, E, B
-        with torch.no_grad():
-            g.row_ptr[:N + 1].copy_(plan.row_ptr)
-            g.mol_ptr[:B + 1].copy_(plan.mol_ptr[:B + 1])
-            g.batch[:N].copy_(plan.b32)
-            g.pos[:N].copy_(plan.pos)
-            if z is not None:
-                g.z[:N].copy_(z)
-            if Q:
-                g.offsets[E:].zero_()
-                g.cell_offsets[E:].zero_()
-                g.order[E:].fill_(-1)
-        EdgeGraph._edges_pbc_fill(plan, g)
-        call("eqf_graph_pad_tail", N, E, n_cap, e_cap, B, _P(g.row_ptr), _P(g.src), _P(g.dst), _P(g.batch), _P(g.mol_ptr),
-             _P(g.pos), _P(g.z), _P(g.node_mask), _P(g.graph_mask), st)
-        call("eqf_csr_by_source_multi", _P(g.src), _P(g.row_ptr), _P(g.mol_ptr), B + 1, max(plan.max_mol_nodes, P, 1),
-             _P(g.src_perm), _P(g.src_ptr), st)
-        return g
+            return EdgeGraph._build_exact(_GIVEN_PBC, plan, into)
+        return EdgeGraph._build_padded(_GIVEN_PBC, plan, capacity, into, z)
 
     @staticmethod
     def from_edges_pbc(pos, cell, batch, edge_index, cell_offsets, neighbors, num_graphs=None, into=None, capacity=None, z=None):
@@ -557,3 +468,12 @@ class EdgeGraph:
         dst = _i32(edge_dst[order])
         row_ptr = _ptr_from_counts(torch.bincount(dst.to(torch.int64), minlength=N))
         return EdgeGraph(N, src, dst, row_ptr, batch, num_graphs), order
+
+
+_PBC_EDGE = (("offsets", (3,), torch.float32, 0), ("cell_offsets", (3,), torch.int32, 0))
+_PBC_TOO_LARGE = "padded periodic graphs need structures (the phantom one included) of at most %d nodes"
+_SEARCH = _Source(EdgeGraph._radius_fill, (), "eqf_csr_by_source", False, False, False,
+                  "padded radius graphs need molecules (the phantom one included) of at most %d nodes")
+_SEARCH_PBC = _Source(EdgeGraph._pbc_fill, _PBC_EDGE, "eqf_csr_by_source_multi", True, False, False, _PBC_TOO_LARGE)
+_GIVEN_PBC = _Source(EdgeGraph._edges_pbc_fill, _PBC_EDGE + (("order", (), torch.int32, -1),), "eqf_csr_by_source_multi", True,
+                     True, True, _PBC_TOO_LARGE)

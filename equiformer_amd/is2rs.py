@@ -18,8 +18,8 @@ configuration uses them), and the OCP trainer around the step (loaders, EMA, eva
 import torch
 
 from . import ops
-from .capture import BucketedTrainStep, given_edge_fields
-from .dens import step_seed  # noqa: F401  (re-exported: the seed of step k)
+from .capture import BucketedTrainStep, _MirrorsBucketed, _refuse_reducer, given_edge_fields
+from .droppath import step_seed  # noqa: F401  (re-exported: the seed of step k)
 
 STATS = ("loss_e", "loss_aux", "n_free", "energy_mae", "energy_mse", "energy_within_threshold", "pos_mae", "unused")
 
@@ -93,7 +93,7 @@ class IS2RSLoss:
                               row_mask=row_mask, stats_out=self.stats)
 
 
-class IS2RSTrainStep:
+class IS2RSTrainStep(_MirrorsBucketed):
     """ts = IS2RSTrainStep(model, optimizer, loss, radius, max_num_neighbors, interpolate=True, seed=0, total_steps=None,
                            auxiliary_task_weight=None, **bucket_kwargs)
        l = ts.step(batch)   # batch: mapping with pos, pos_relaxed [N, 3], atomic_numbers, tags [N], batch [N] (ascending),
@@ -119,8 +119,7 @@ class IS2RSTrainStep:
 
     def __init__(self, model, optimizer, loss, radius, max_num_neighbors, interpolate=True, seed=0, total_steps=None,
                  auxiliary_task_weight=None, **bucket_kwargs):
-        if getattr(optimizer, "_reducer", None) is not None:
-            raise ValueError("IS2RSTrainStep: data-parallel steps stay eager (the reducer's collectives are not captured)")
+        _refuse_reducer(optimizer, "IS2RSTrainStep")
         if not getattr(model, "use_auxiliary_task", False):
             raise ValueError("IS2RSTrainStep: the model has no IS2RS head (use_auxiliary_task=True)")
         self.model, self.loss = model, loss
@@ -138,10 +137,6 @@ class IS2RSTrainStep:
     def _forward_loss(self, g, view):
         out = self.model(view, graph=g, offsets=view.offsets)
         return self.loss(out[0][:view.B], out[1], view, row_mask=view.node_mask, num_graphs=view.B)
-
-    eager_steps = property(lambda self: self.bucketed.eager_steps)
-    captures = property(lambda self: self.bucketed.captures)
-    replays = property(lambda self: self.bucketed.replays)
 
     def step(self, batch):
         k = self.steps

@@ -145,7 +145,7 @@ class GraphAttentionTransformerOC20(_Trunk):
         if graph is None:
             graph, offsets = self._graph(data, pos, batch)
         elif offsets is None:
-            offsets = getattr(graph, "offsets", None)
+            offsets = graph.offsets
         atom_embedding, _, _ = self.atom_embed(data.atomic_numbers.long())
         tag_embedding, _, _ = self.tag_embed(data.tags.long())
         node_features, ectx = self._trunk_features(atom_embedding + tag_embedding, pos, graph, offsets)
