@@ -562,13 +562,15 @@ void launch_rows_cfg(const RowsArgs& a, hipStream_t st) {
 template <int AMODE, int BMODE>
 int launch_rows(RowsArgs& a, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0) return 0;
-  const int bn = a.N > 64 ? 128 : (a.N > 32 ? 64 : 32);
+  int bn = a.N > 64 ? 128 : (a.N > 32 ? 64 : 32);
   // 64-row tiles when 128-row tiles would leave most of the 256 CUs without a workgroup
   const int d = AMODE == A_DTP ? a.dtp.d3 : 1;
   const long tiles128 = (long)eqf_cdiv(a.M, (128 / d) * d) * eqf_cdiv(a.N, bn);
   int bm = (bn >= 64 && tiles128 < 4096) ? 64 : 128;
   if (AMODE == A_DTP) {
-    if (bn >= 64 && ((128 / d) > 8 * ROWS_PAIRS || (128 / d) * a.dtp.m_len > MAX_MTILE)) bm = 64;
+    // a 128-row tile holds more edges than the loader generates (8 ROWS_PAIRS) or than the coupling tile stages: 64 rows.  The
+    // only 32-column configuration has 128 rows, so N <= 32 then takes the 64 x 64 tile with its columns past N masked
+    if ((128 / d) > 8 * ROWS_PAIRS || (128 / d) * a.dtp.m_len > MAX_MTILE) bm = 64, bn = bn < 64 ? 64 : bn;
     a.dtp.ept = bm / d;
     a.rows_per_tile = a.dtp.ept * d;
     if (a.dtp.ept > 8 * ROWS_PAIRS || a.dtp.ept * a.dtp.m_len > MAX_MTILE) return EQF_E_UNSUPPORTED;

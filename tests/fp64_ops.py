@@ -4,7 +4,7 @@ Each function states one operator of `equiformer_amd.ops` from its definition, a
 layout (a row holds its irreps segments one after the other, the segment of degree l stored as [2l+1][mul]).  Nothing
 here imports `equiformer_amd.ops` or touches HIP; gradients come from autograd on these functions.
 tests/test_fp64_ops.py pins them on the CPU against the oracle modules (e3nn layout) at 1e-12, tests/test_gpu_op_edges.py
-compares the HIP kernels with them.  The functions work in whatever dtype their inputs have: float64 is the reference,
+and tests/test_gpu_dp_edges.py (kv_split, kv_merge, dp_logits) compare the HIP kernels with them.  The functions work in whatever dtype their inputs have: float64 is the reference,
 the same call in float32 is the yardstick for what fp32 arithmetic can deliver on an input (`yardstick` below).
 
 Inputs of a comparison are float32-rounded values cast to double (`f32r`), so input rounding is never counted as
@@ -274,6 +274,63 @@ def attn_aggregate(logit, value, row_ptr, H, layout, keep=None):
     wgt = alpha if keep is None else alpha * keep
     hoc = head_of_column(layout, H).to(value.device)
     return segment_sum(value * wgt[:, hoc], row_ptr), alpha
+
+
+# ------------------------------------------------------------------------------------------------- dot-product attention
+# `segs` describes the q / k / v row of all H heads: in the segment of degree l the channel index is (head, channel of the
+# head), so mul = H * mul_of_head.  The key/value row holds 2H heads per segment, [2l+1][2 mul]: the first `mul` channels
+# of every m-row are the keys, the last `mul` the values.
+def _head_segs(segs, H):
+    lay = segs if isinstance(segs, Segs) else Segs(segs)
+    assert all(mul % H == 0 for mul, _ in lay.segs), (lay.segs, H)
+    return lay
+
+
+def kv_split(kv, segs, H):
+    """kv [E, 2 D] -> (k, v), [E, D] each"""
+    lay = _head_segs(segs, H)
+    k, v, off = [], [], 0
+    for mul, l in lay.segs:
+        d = 2 * l + 1
+        f = kv[:, off:off + 2 * mul * d].reshape(-1, d, 2 * mul)
+        k.append(f[:, :, :mul].reshape(-1, d * mul))
+        v.append(f[:, :, mul:].reshape(-1, d * mul))
+        off += 2 * mul * d
+    return torch.cat(k, dim=1), torch.cat(v, dim=1)
+
+
+def kv_merge(k, v, segs, H):
+    """the inverse of kv_split; a missing k or v is zero"""
+    lay = _head_segs(segs, H)
+    given = k if k is not None else v
+    k = torch.zeros_like(given) if k is None else k
+    v = torch.zeros_like(given) if v is None else v
+    out = []
+    for (mul, l), off in zip(lay.segs, lay.offsets):
+        d = 2 * l + 1
+        out.append(torch.cat([k[:, off:off + mul * d].reshape(-1, d, mul), v[:, off:off + mul * d].reshape(-1, d, mul)],
+                             dim=2).reshape(-1, 2 * mul * d))
+    return torch.cat(out, dim=1)
+
+
+def dp_scales(segs, H):
+    """scale_s = 1 / sqrt(sum_s mul_s / H) / sqrt(2 l_s + 1): the ScaleFactor of the dot-product attention, per segment"""
+    lay = _head_segs(segs, H)
+    num = sum(mul // H for mul, _ in lay.segs)
+    return [1.0 / (num ** 0.5 * (2 * l + 1) ** 0.5) for _, l in lay.segs]
+
+
+def dp_logits(q, k, dst, segs, H):
+    """logit[e, h] = sum_s scale_s sum_{m, c} q[dst[e], s, m, h, c] k[e, s, m, h, c]"""
+    lay = _head_segs(segs, H)
+    qd = q[dst.long()]
+    logit = 0.0
+    for (mul, l), off, sc in zip(lay.segs, lay.offsets, dp_scales(lay, H)):
+        d = 2 * l + 1
+        qs = qd[:, off:off + mul * d].reshape(-1, d, H, mul // H)
+        ks = k[:, off:off + mul * d].reshape(-1, d, H, mul // H)
+        logit = logit + sc * (qs * ks).sum(dim=(1, 3))
+    return logit
 
 
 # ------------------------------------------------------------------------------------------------- shared cases

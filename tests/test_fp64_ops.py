@@ -1,6 +1,11 @@
 """The float64 restatements of tests/fp64_ops.py against what the project already trusts on the CPU: the oracle modules
 (e3nn layout), torch.nn.functional and the layout permutations of equiformer_amd.layout -- on the same ragged inputs
-that tests/test_gpu_op_edges.py feeds the HIP kernels.  Agreement is at 1e-12 of the result's scale.  No GPU."""
+that tests/test_gpu_op_edges.py feeds the HIP kernels.  Agreement is at 1e-12 of the result's scale.  No GPU.
+
+Last two parts: the dot-product attention restatements (kv_split, kv_merge, dp_logits) against the oracle's own pieces on the
+head layouts of tests/dp_edge_cases.py, and negative controls for tests/test_gpu_dp_edges.py and tests/test_gpu_dtp_edges.py: a
+restatement that is wrong in the way a kernel could be (heads exchanged, another segment's scale, keys for values, a wrong
+out_ch, the neighbouring channel's weight) must miss, on the GPU tests' inputs, the bound those tests apply, by >= 10 x."""
 import os
 import sys
 
@@ -8,8 +13,11 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dp_edge_cases as dpc  # noqa: E402
+import dtp_edge_cases as dtc  # noqa: E402
 import fp64_ops as fo  # noqa: E402
-from equiformer_amd import so3  # noqa: E402
+import fp64_tp as tp  # noqa: E402
+from equiformer_amd import ops, so3  # noqa: E402
 from equiformer_amd.layout import RowLayout  # noqa: E402
 from oracle import e3  # noqa: E402
 from oracle import nets as onets  # noqa: E402
@@ -217,3 +225,141 @@ def test_fold_weight_restatement():
     W, w = _randn((int(row_start[-1]),), 31), _randn((len(lens),), 32)
     want = torch.cat([W[row_start[r]:row_start[r + 1]] * w[w_of_row[r]] for r in range(len(lens))])
     assert _close(fo.fold_weight(W, w, row_start, w_of_row), want)
+
+
+# ------------------------------------------------------------------------------------------------- dot-product attention
+def _dp_oracle(q_e3, kv_e3, dst, head_irr, H):
+    """the oracle's own pieces (oracle.nets.DotProductAttention.forward): vec2heads on irreps_head * H and * 2H, the narrow,
+    the ScaleFactor and the einsum"""
+    oh = e3.Irreps(head_irr)
+    chan = 1.0 / (oh.num_irreps ** 0.5)
+    scale = torch.cat([torch.full((mul * ir.dim,), chan / ir.dim ** 0.5, dtype=torch.float64) for mul, ir in oh])
+    q = onets.vec2heads(q_e3, oh, H) * scale
+    kv = onets.vec2heads(kv_e3, oh, 2 * H)
+    k, v = kv[:, :H], kv[:, H:]
+    return torch.einsum("bik,bik->bi", q[dst], k), onets.heads2vec(k, oh), onets.heads2vec(v, oh)
+
+
+@pytest.mark.parametrize("head_irr,H", dpc.HEADS)
+def test_dp_restatements_match_oracle(head_irr, H):
+    """kv_split, its inverse and dp_logits: values, gradients and second derivatives on the ragged graph's first rows"""
+    seg, seg2 = fo.all_heads_layout(head_irr, H), fo.all_heads_layout(head_irr, 2 * H)
+    lay, lay2 = RowLayout(dpc.irreps_str(seg)), RowLayout(dpc.irreps_str(seg2))  # the layouts the kernels are given
+    assert lay.segs == seg.segs and all(m % H == 0 and (m // H) % 4 == 0 for m, _ in lay.segs) and H <= 8
+    assert dpc.groups(head_irr, H) * 4 == seg.dim and lay2.dim == 2 * seg.dim
+    graph = dpc.graph("ragged")
+    E = 200
+    dst = graph.dst.long()[:E]
+    N = int(dst.max()) + 2
+    p, p2 = seg.perm_from_e3nn(), seg2.perm_from_e3nn()
+    inv, inv2 = torch.empty_like(p), torch.empty_like(p2)
+    inv[p], inv2[p2] = torch.arange(p.numel()), torch.arange(p2.numel())
+    d = dpc.inputs(head_irr, H, N, E)
+    qc, kvc = d["q"].clone().requires_grad_(True), d["kv"].clone().requires_grad_(True)
+    qe, kve = d["q"][:, inv].clone().requires_grad_(True), d["kv"][:, inv2].clone().requires_grad_(True)
+    lw, kw, vw = _dp_oracle(qe, kve, dst, head_irr, H)
+    k, v = fo.kv_split(kvc, seg, H)
+    lg = fo.dp_logits(qc, k, dst, seg, H)
+    assert torch.equal(k.detach(), kw.detach()[:, p]) and torch.equal(v.detach(), vw.detach()[:, p])
+    assert _close(lg, lw)
+    assert torch.equal(fo.kv_merge(k, v, seg, H).detach(), kvc.detach())
+    zero = torch.zeros_like(k)
+    assert torch.equal(fo.kv_merge(k, None, seg, H).detach(), fo.kv_merge(k, zero, seg, H).detach())
+    assert torch.equal(fo.kv_split(fo.kv_merge(None, v, seg, H), seg, H)[0].detach(), zero.detach())
+    gw = torch.autograd.grad([lw, kw, vw], [qe, kve], [d["cl"], d["ck"][:, inv], d["cv"][:, inv]], create_graph=True)
+    gg = torch.autograd.grad([lg, k, v], [qc, kvc], [d["cl"], d["ck"], d["cv"]], create_graph=True)
+    assert _close(gg[0], gw[0][:, p]) and _close(gg[1], gw[1][:, p2])
+    hw = torch.autograd.grad((gw[0] * d["a"][:, inv]).sum() + (gw[1] * d["b"][:, inv2]).sum(), [qe, kve])
+    hg = torch.autograd.grad((gg[0] * d["a"]).sum() + (gg[1] * d["b"]).sum(), [qc, kvc])
+    assert _close(hg[0], hw[0][:, p]) and _close(hg[1], hw[1][:, p2])
+
+
+def _dp_eval(head_irr, H, dtype, q=None, kv=None, swap=None):
+    """(logit, k, v, dq, dk) of the restatement on the GPU test's ragged inputs"""
+    seg = fo.all_heads_layout(head_irr, H)
+    graph = dpc.graph("ragged")
+    dst = graph.dst.long()
+    d = dpc.inputs(head_irr, H, graph.N, graph.E)
+    q = (d["q"] if q is None else q).to(dtype).requires_grad_(True)
+    k, v = fo.kv_split((d["kv"] if kv is None else kv).to(dtype), seg, H)
+    k = k.detach().requires_grad_(True)
+    kk = k if swap is None else swap(k)
+    lg = fo.dp_logits(q, kk, dst, seg, H)
+    dq, dk = torch.autograd.grad(lg, [q, k], d["cl"].to(dtype))
+    return dict(logit=lg.detach(), k=k.detach(), v=v.detach(), dq=dq, dk=dk)
+
+
+@pytest.mark.parametrize("head_irr,H", [h for h in dpc.HEADS if h[1] > 1 and len(fo.Segs(h[0]).segs) > 1])
+def test_dp_wrong_restatements_miss_the_gpu_bound(head_irr, H):
+    """negative controls for tests/test_gpu_dp_edges.py, on its ragged inputs: two heads exchanged in one segment, the scale of
+    one segment on another, keys and values exchanged in one segment -- each leaves a per-row error far above the bound
+    max(1e-5, 4 x float32 yardstick) that test applies to the quantity"""
+    seg = fo.all_heads_layout(head_irr, H)
+    graph = dpc.graph("ragged")
+    d = dpc.inputs(head_irr, H, graph.N, graph.E)
+    ref, y32 = _dp_eval(head_irr, H, torch.float64), _dp_eval(head_irr, H, torch.float32)
+    lim = {n: dpc.bound(fo.per_row_rel(y32[n], ref[n])) for n in ("logit", "dq")}
+    lim["dk"] = lim["k"] = lim["v"] = dpc.bound()
+    assert all(v < 1e-4 for v in lim.values()), lim  # the yardstick leaves the bounds near the plain 1e-5
+    last = len(seg.segs) - 1
+    wrong = {"heads": _dp_eval(head_irr, H, torch.float64, swap=lambda k: dpc.swap_heads(k, seg, H, last, 0, H - 1)),
+             "scale": _dp_eval(head_irr, H, torch.float64, q=dpc.rescale_segment(d["q"], seg, H, last, 0)),
+             "kv": _dp_eval(head_irr, H, torch.float64, kv=dpc.swap_kv(d["kv"], seg, last))}
+    seen = {(w, n): fo.per_row_rel(wrong[w][n], ref[n]) / lim[n]
+            for w, n in (("heads", "logit"), ("heads", "dq"), ("heads", "dk"), ("scale", "logit"), ("scale", "dk"),
+                         ("kv", "k"), ("kv", "v"), ("kv", "logit"))}
+    print(seen)
+    assert all(v >= 10.0 for v in seen.values()), seen
+
+
+# ------------------------------------------------------------------------------------------------- un-fused tensor product
+def test_dtp_edge_tables_are_what_the_gpu_test_says():
+    """the properties tests/test_gpu_dtp_edges.py relies on, from the tables and the source constants"""
+    import re
+    w = {n: dtc.table(n).weight_numel for n in dtc.TABLES}
+    assert w["narrow"] == 72 and w["two_blocks"] == 480 and w["two_blocks"] > 256 >= w["narrow"]
+    t = dtc.table("l3")
+    assert sum(m for m, _ in t.layout_in.segs) > 256 and max(p["l1"] for p in t.paths) == 3
+    assert dtc.table("parity").has_odd and all(dtc.table(n).in_covered for n in dtc.TABLES if n != "uncovered")
+    t = dtc.table("uncovered")
+    assert not t.in_covered and {p["in_off"] for p in t.paths} == {0} and t.layout_in.offsets == [0, 8]
+    src = open(os.path.join(os.path.dirname(os.path.abspath(dtc.__file__)), "..", "equiformer_amd", "csrc", "gemm.hip")).read()
+    assert int(re.search(r"constexpr int ROWS_PAIRS = (\d+);", src).group(1)) == dtc.ROWS_PAIRS
+    assert int(re.search(r"constexpr int MAX_MTILE = (\d+);", src).group(1)) == dtc.MAX_MTILE
+    K = {n: [k for k, _ in dtc.table(n).layout_out.segs] for n in dtc.LIN_TABLES}
+    assert K["k96"] == [96, 192, 192] and K["k288"] == [128, 256, 288] and len(K["deg3"]) == 4
+    for n in dtc.LIN_TABLES:  # the spec accepts every consumer, and every tile the dispatch picks fits the loader and the LDS tile
+        t = dtc.table(n)
+        for N in dtc.LIN_N:
+            assert ops.DtpLinearSpec.make(t, dtc.consumer(n, N)) is not None
+            for (_, l3), par in zip(t.layout_out.segs, t.layout_out.par):
+                for E in dtc.lin_edges(t.lmax_sh):
+                    dtc.tile_of(t, l3, par, N, E)
+    # the edges-per-tile values the GPU test is meant to straddle
+    t = dtc.table("deg3")
+    assert [dtc.tile_of(t, l, 1, 64, 9)[2] for l in range(4)] == [64, 21, 12, 9]
+    assert [dtc.tile_of(t, l, 1, 32, 9) for l in range(4)] == [(64, 64, 64), (128, 32, 42), (128, 32, 25), (128, 32, 18)]
+    assert {dtc.tn_tile_of(K, N) for K in (96, 192) for N in (32, 64)} == {(32, 32), (32, 64), (64, 32), (64, 64)}
+
+
+@pytest.mark.parametrize("kind,use_w", [("out_ch", True), ("out_ch", False), ("w", True)])
+def test_dtp_wrong_tables_miss_the_gpu_bound(kind, use_w):
+    """negative controls for tests/test_gpu_dtp_edges.py on its inputs: a wrong out_ch of one path, and w of the neighbouring
+    channel, against the bound max(plain, 4 x float32 yardstick) of every quantity they move"""
+    t = dtc.table("two_blocks")
+    bad = dtc.wrong_table(t, kind)
+    for E in (2, 257):
+        d = dtc.inputs("two_blocks", E)
+        ins = [d["x"], d["M"]] + ([d["w"]] if use_w else [])
+        names = ["out", "dx", "dM"] + (["dw"] if use_w else [])
+        fn = lambda tab: (lambda x, M, w=None: tp.product(tab, x, M, w))  # noqa: E731
+        ro, rg, yo, yg = fo.yardstick(fn(t), ins, [d["go"]])
+        wo, wg = fo.evaluate(fn(bad), ins, [d["go"]], torch.float64)
+        seen = {}
+        for n, r, y, b in zip(names, ro + rg, yo + yg, wo + wg):
+            lim = max(dtc.BOUNDS[n], dtc.YARD_FACTOR * fo.per_row_rel(y, r))
+            assert lim < 1e-4, (n, lim)
+            seen[n] = fo.per_row_rel(b, r) / lim
+        print(kind, use_w, E, seen)
+        moved = ["out", "dx", "dM"] + (["dw"] if (use_w and kind == "w") else [])
+        assert all(seen[n] >= 10.0 for n in moved), seen
