@@ -186,6 +186,8 @@ SIGNATURES = {
     "eqf_is2rs_loss_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_int, _d, _d, _d, _d, _d,
                            _d, _d, _d, c_fp, c_fp, c_fp],
     "eqf_metrics_accumulate": [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, _d, _d, _d, c_fp, c_fp],
+    "eqf_ef_loss_fwd": [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, _d, _d, _d, c_fp, c_fp, c_fp],
+    "eqf_ef_loss_bwd": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, _d, _d, c_fp, c_fp, c_fp],
     "eqf_prof_enable": [ctypes.c_char_p],
     "eqf_prof_report": [ctypes.c_char_p, c_int],
 }

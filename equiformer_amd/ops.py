@@ -1968,6 +1968,50 @@ def metrics_accumulate(acc, pred_y, y, n_graphs, task_mean, task_std, threshold,
          float(task_std), float(threshold), ctypes.c_void_p(acc.data_ptr()), _stream())
 
 
+EF_CRITERIA = {"l1": 0, "l2": 1, "l2mae": 2}  # EQF_LOSS_L1 / _L2 / _L2MAE of include/equiformer_hip.h
+
+
+def ef_loss(pred_y, y, n_graphs, weights, task_mean, task_std, criterion="l1", pred_dy=None, dy=None, row_mask=None, acc=None,
+            threshold=0.02):
+    """loss (0-dim) = w_e C(pred_y[:n_graphs], (y - mean) / std) + w_f C(pred_dy, dy / std) over the real rows
+    (include/equiformer_hip.h eqf_ef_loss_fwd) [ref: engine.py:71, main_md17.py:384-386, energy_trainer_v2.py:413-442]: one
+    launch forward, one backward, nothing read back.  criterion: "l1", "l2" (MSE) or "l2mae" (L1 on energies, mean row norm
+    on forces).  pred_y / y: fp32 with at least n_graphs rows, of which the first n_graphs count (a padded batch carries the
+    phantom molecule's row; its gradient is an exact 0).  weights: [2] fp32 DEVICE tensor {energy, force}.  pred_dy / dy:
+    [N, 3] fp32, None = no force term; row_mask: [N] fp32, 1 real / 0 phantom (None: all real).  acc: the caller's ten fp64
+    running sums of evaluate.Meter (`SUMS`), to which the same launch adds this batch (None: none).  First order only.
+    The launches are written in equiformer_amd/train.py, beside the training loops that use them."""
+    from .train import _EFLoss
+    if criterion not in EF_CRITERIA:
+        raise ValueError("ef_loss: criterion %r is not one of %s" % (criterion, sorted(EF_CRITERIA)))
+    y = y.detach()
+    _chk(pred_y, y, weights, pred_dy, dy, row_mask)
+    n_graphs = int(n_graphs)
+    if n_graphs < 1 or pred_y.numel() < n_graphs or y.numel() < n_graphs:
+        raise ValueError("ef_loss: pred_y %s, y %s, n_graphs %d" % (tuple(pred_y.shape), tuple(y.shape), n_graphs))
+    if (pred_dy is None) != (dy is None):
+        raise ValueError("ef_loss: pred_dy and dy come together")
+    if pred_dy is None and row_mask is not None:
+        raise ValueError("ef_loss: a row_mask without forces")
+    if pred_dy is not None:
+        dy = dy.detach()
+        N = pred_dy.shape[0]
+        if tuple(pred_dy.shape) != (N, 3) or tuple(dy.shape) != (N, 3) or (row_mask is not None and row_mask.numel() != N):
+            raise ValueError("ef_loss: pred_dy %s, dy %s, row_mask %s" % (
+                tuple(pred_dy.shape), tuple(dy.shape), None if row_mask is None else tuple(row_mask.shape)))
+    if weights.numel() != 2 or weights.dtype != torch.float32:
+        raise ValueError("weights: 2 fp32 device words {energy, force}")
+    if acc is not None:
+        if not acc.is_cuda:
+            raise HipOnlyError("the Equiformer hot path runs on MI355X only (got a %s tensor); there is no CPU fallback" % acc.device)
+        if acc.dtype != torch.float64 or acc.numel() != METRICS_SUMS or not acc.is_contiguous():
+            raise ValueError("acc: %d contiguous fp64 device words" % METRICS_SUMS)
+    if not float(task_std) > 0.0:
+        raise ValueError("ef_loss: task_std must be positive, got %r" % (task_std,))
+    return _EFLoss.apply(pred_y, pred_dy, y, dy, row_mask, weights, acc, n_graphs, EF_CRITERIA[criterion], float(task_mean),
+                         float(task_std), float(threshold))
+
+
 class _RbfGaussian(Function):
     @staticmethod
     def forward(ctx, length, mean, std, weight, bias, cutoff):

@@ -827,6 +827,40 @@ int eqf_metrics_accumulate(const float* pred_y, const float* y, int n_graphs, co
                            const float* node_mask, int N, double task_mean, double task_std, double threshold, double* acc,
                            void* stream);
 
+/* The energy / force training loss of the QM9, MD17 and plain IS2RE recipes, with the meters folded in, one launch.
+ * [ref: engine.py:71 (QM9: criterion(pred, (y - mean) / std)), :85-87 its loss and MAE meters; main_md17.py:384-386 (ONE
+ * criterion on both terms), :392-400 its four meters, L2MAELoss :126-129; energy_trainer_v2.py:413-459 the energy term of
+ * _compute_loss and _compute_metrics]  With d_b = pred_y[b] - (y[b] - task_mean) / task_std over b < n_graphs and
+ * d_ic = pred_dy[i,c] - dy[i,c] / task_std over the n real rows i < N (row_mask[i] != 0; row_mask NULL: every row):
+ *   C = EQF_LOSS_L1:    L_e = mean_b |d_b|,  L_f = sum_ic |d_ic| / (3 n)        (torch.nn.L1Loss)
+ *   C = EQF_LOSS_L2:    L_e = mean_b d_b^2,  L_f = sum_ic d_ic^2 / (3 n)        (torch.nn.MSELoss)
+ *   C = EQF_LOSS_L2MAE: L_e = mean_b |d_b|,  L_f = sum_i ||d_i||_2 / n          (L2MAELoss: on [B, 1] energies it is L1)
+ *   loss[0] = weights[0] L_e + weights[1] L_f
+ * pred_dy == NULL drops the force term (QM9, IS2RE); n == 0 makes it an exact 0.  When acc != NULL the launch also ADDS the
+ * batch to the ten running sums of eqf_metrics_accumulate, with the same formulas and order (acc[0..4] from the energies,
+ * acc[5..9] from the real force rows; task_std, threshold as there).  Rows >= n_graphs and rows whose row_mask is 0 are never
+ * read: a NaN there reaches nothing.  `weights` [2] is DEVICE memory: a captured launch sees a weight the host changed
+ * between two replays.  One workgroup, fp64 arithmetic from the fp32 inputs, fixed-order reduction: no atomics, no
+ * workspace, two calls give the same bits.  n_graphs < 1, N < 0, an unknown criterion, task_std <= 0, pred_dy without dy
+ * and a missing pred_y / y / weights / loss are argument errors, refused before anything is launched.  Enqueue-only. */
+#define EQF_LOSS_L1 0
+#define EQF_LOSS_L2 1
+#define EQF_LOSS_L2MAE 2
+int eqf_ef_loss_fwd(const float* pred_y, const float* y, int n_graphs, const float* pred_dy, const float* dy,
+                    const float* row_mask, int N, const float* weights, int criterion, double task_mean, double task_std,
+                    double threshold, float* loss, double* acc, void* stream);
+/* d_pred_y[n_rows_y]: g weights[0] / n_graphs sign(d_b) (L1, L2MAE) or 2 g weights[0] / n_graphs d_b (L2) for b < n_graphs,
+ * exactly 0 for n_graphs <= b < n_rows_y (the phantom molecule's row).  d_pred_dy[N, 3]: g weights[1] / (3 n) sign(d_ic)
+ * (L1), 2 g weights[1] / (3 n) d_ic (L2), g weights[1] / n d_i / ||d_i|| (L2MAE); exactly 0 on phantom rows, where the
+ * difference vanishes (sign(0) = 0; under L2MAE a row with ||d_i|| = 0: the subgradient torch takes) and everywhere when
+ * n == 0.  g = d_loss[0], read on the device.  The count n is RECOMPUTED here from row_mask with the forward's predicate:
+ * the backward reads nothing the forward wrote, so a later forward cannot change it.  First order only: pred_dy carries the
+ * second-order graph of the forces, the loss does not.  Argument errors as the forward, plus n_rows_y < n_graphs and pred_dy
+ * without d_pred_dy.  [ref: the `loss.backward()` of engine.py:77 and main_md17.py:389] */
+int eqf_ef_loss_bwd(const float* d_loss, const float* pred_y, const float* y, int n_graphs, int n_rows_y,
+                    const float* pred_dy, const float* dy, const float* row_mask, int N, const float* weights, int criterion,
+                    double task_mean, double task_std, float* d_pred_y, float* d_pred_dy, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; used by bench.py for the roofline line)
  * ------------------------------------------------------------------------------------------- */
