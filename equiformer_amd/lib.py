@@ -66,6 +66,8 @@ _P_PATHS = ctypes.POINTER(EqfDtpPaths)
 _PP = ctypes.POINTER(ctypes.c_void_p)
 _f = ctypes.c_float
 _d = ctypes.c_double
+_P_INT = ctypes.POINTER(c_int)  # host arrays read when the launch is built
+_P_DBL = ctypes.POINTER(_d)
 _u64 = ctypes.c_ulonglong
 _long = ctypes.c_long
 
@@ -188,6 +190,7 @@ SIGNATURES = {
     "eqf_metrics_accumulate": [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, _d, _d, _d, c_fp, c_fp],
     "eqf_ef_loss_fwd": [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, _d, _d, _d, c_fp, c_fp, c_fp],
     "eqf_ef_loss_bwd": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, _d, _d, c_fp, c_fp, c_fp],
+    "eqf_meter_fold": [c_fp, c_int, c_fp, c_int, _P_INT, _P_INT, _P_DBL, c_fp, c_fp],
     "eqf_prof_enable": [ctypes.c_char_p],
     "eqf_prof_report": [ctypes.c_char_p, c_int],
 }

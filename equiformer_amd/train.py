@@ -1,6 +1,7 @@
-"""Training loops on the HIP path for the three recipes bench.py measures: QM9, MD17 and plain IS2RE (no auxiliary head).
+"""Training loops on the HIP path for the five recipes: QM9, MD17 and plain IS2RE (no auxiliary head), DeNS and IS2RE + IS2RS.
 [ref: engine.py:30-107 train_one_epoch (QM9), main_md17.py:361-422 train_one_epoch, the energy term of
-oc20/trainer/energy_trainer_v2.py:413-459 with base_trainer_v2.py's per-step scheduler]
+oc20/trainer/energy_trainer_v2.py:413-459 with base_trainer_v2.py's per-step scheduler, main_md17_dens.py:349-450
+train_one_epoch (DeNS), energy_trainer_v2.py:240-317 the training loop of the _aux configurations (IS2RE + IS2RS)]
 
 The reference loops launch a loss written in ATen and stop the GPU for two (QM9) to four (MD17) `.item()` read-backs per step.
 Here, per step:
@@ -15,7 +16,12 @@ the batch size, which is the ratio of two sums.
 Schedules: `lr_lambda_cosine` / `lr_lambda_multistep` are the OC20 trainer's per-step factors, `cosine_epoch_lr` the per-epoch
 timm cosine schedule of the QM9 and MD17 drivers -- pure host functions.  A captured AdamW reads lr from its device word, so a
 `param_group["lr"]` written before a step reaches the replay.  `compute_stats` is engine.compute_stats on the count half of the
-GPU graph build."""
+GPU graph build.
+
+The DeNS and IS2RE + IS2RS loops run the steps of dens.py / is2rs.py, whose fused losses leave one step's means in an fp32
+`stats` buffer.  Their metered losses (`DeNSMeteredLoss`, `IS2RSMeteredLoss`) fold those means into `RunningMeters`, fp64
+(sum, count) pairs on the device (eqf_meter_fold, csrc/meters.hip: one launch inside forward_loss, so an eager, captured or
+replayed step is counted once), and the loops read the pairs back once per log line and once at the end."""
 import ctypes
 import math
 import time
@@ -24,9 +30,11 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import is2rs, ops
 from .capture import BucketedTrainStep, _MirrorsBucketed, _refuse_reducer
+from .dens import DeNSLoss, DeNSTrainStep
 from .evaluate import Meter, _avg
+from .is2rs import IS2RSLoss, IS2RSTrainStep
 from .lib import call
 from .ops import _c, _p, _stream
 
@@ -297,6 +305,228 @@ def train_one_epoch_oc20(step, loader, lr_lambda=None, print_freq=100, log=None,
     return f["oc20"], f["oc20_loss"]
 
 
+# ------------------------------------------------------------------------------------------------------------ running meters
+METERS_MAX = 16    # EQF_METERS_MAX
+LOSS = "loss"      # a meter's value: the loss scalar the step returns
+GRAPHS = "graphs"  # a meter's weight: the step's graph count (view.B: constant within a bucket)
+ONE = "one"        # a meter's weight: 1 (one update per step)
+
+# (name, value, weight): value an index into the loss's `stats` or LOSS; weight an index into `stats`, GRAPHS or ONE.
+# DeNS [ref: main_md17_dens.py:411-427]: dens.STATS = loss_e, loss_f, loss_d, n_f, n_d, mae_e, mae_f, mae_d
+DENS_METERS = (("loss_energy", 0, GRAPHS), ("loss_force", 1, 3), ("loss_denoising_pos", 2, 4),
+               ("mae_energy", 5, GRAPHS), ("mae_force", 6, 3), ("mae_denoising_pos", 7, 4))
+# IS2RE + IS2RS [ref: energy_trainer_v2.py:247-288, one update per step]: is2rs.STATS = loss_e, loss_aux, n_free, energy_mae,
+# energy_mse, energy_within_threshold, pos_mae; pos_mae (weighted by n_free) is no reference figure
+IS2RS_METERS = (("loss", LOSS, ONE), ("energy_mae", 3, ONE), ("energy_mse", 4, ONE), ("energy_within_threshold", 5, ONE),
+                ("pos_mae", 6, 2))
+
+
+class RunningMeters:
+    """meters = RunningMeters(spec, device)     spec: ((name, value, weight), ...), as DENS_METERS / IS2RS_METERS
+       meters.fold(stats, loss, graphs)        # every step: one launch (eqf_meter_fold), nothing read back
+       meters.averages()                       # {name: evaluate.Average}: one read-back
+
+    The reference's AverageMeter per name [ref: engine.py:23-27 update(val, n)]: meter i adds value * weight and weight to the
+    fp64 pair acc[2i], acc[2i + 1] of ONE device buffer (allocated here, outside any capture: a captured fold writes its
+    address), and is left as it is when the weight is 0.  The sums equal a host AverageMeter fed the same fp32 values, bit for
+    bit.  `reads` counts the read-backs."""
+
+    def __init__(self, spec, device):
+        spec = tuple((str(n), v, w) for n, v, w in spec)
+        if not 1 <= len(spec) <= METERS_MAX:
+            raise ValueError("RunningMeters: 1 to %d meters, got %d" % (METERS_MAX, len(spec)))
+        for n, v, w in spec:
+            if not (v == LOSS or (isinstance(v, int) and v >= 0)) or not (w in (GRAPHS, ONE) or (isinstance(w, int) and w >= 0)):
+                raise ValueError("RunningMeters: meter %r has value %r, weight %r" % (n, v, w))
+        self.spec, self.names = spec, tuple(n for n, _, _ in spec)
+        M = len(spec)
+        self.acc = torch.zeros(2 * M, dtype=torch.float64, device=device)
+        self._value = (ctypes.c_int * M)(*[-1 if v == LOSS else v for _, v, _ in spec])
+        self._weight = (ctypes.c_int * M)(*[-1 if w in (GRAPHS, ONE) else w for _, _, w in spec])
+        self.reads = 0
+
+    def fold(self, stats, loss, graphs=None):
+        """stats: the loss's fp32 stats buffer; loss: its fp32 scalar; graphs: the step's graph count (meters weighted by
+        GRAPHS).  Enqueue-only: legal inside a capture, which keeps `graphs` as it was."""
+        if not self.acc.is_cuda:
+            raise ops.HipOnlyError("RunningMeters.fold runs on MI355X only (the meters are on %s)" % self.acc.device)
+        if stats.dtype != torch.float32 or loss.dtype != torch.float32 or loss.numel() != 1 or not stats.is_contiguous():
+            raise ValueError("RunningMeters.fold: stats must be a contiguous fp32 buffer and loss an fp32 scalar")
+        const = []
+        for n, _, w in self.spec:
+            if w == GRAPHS and graphs is None:
+                raise ValueError("RunningMeters.fold: meter %r is weighted by the graph count; pass graphs" % n)
+            const.append(float(graphs) if w == GRAPHS else 1.0)
+        M = len(self.spec)
+        call("eqf_meter_fold", _p(stats), stats.numel(), _p(loss), M, self._value, self._weight, (ctypes.c_double * M)(*const),
+             ctypes.c_void_p(self.acc.data_ptr()), _stream())
+
+    def reset(self):
+        """a fill on the stream"""
+        self.acc.zero_()
+
+    def read(self):
+        """{name: (sum, count)}: the one read-back"""
+        self.reads += 1
+        a = self.acc.tolist()
+        return {n: (a[2 * i], a[2 * i + 1]) for i, n in enumerate(self.names)}
+
+    def averages(self, sums=None):
+        """{name: evaluate.Average(avg, sum, count)} of `sums` (default: read()); a count of 0 gives avg NaN (the reference
+        prints 0 there)"""
+        sums = self.read() if sums is None else sums
+        return {n: _avg(*sums[n]) for n in self.names}
+
+
+class DeNSMeteredLoss(DeNSLoss):
+    """A dens.DeNSLoss that folds every call's stats into `.meters` (RunningMeters of DENS_METERS): after the loss launch, in the
+    same forward, so the step is counted once whether it runs eager, is captured (recorded, not run) or replayed."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.meters = RunningMeters(DENS_METERS, self.stats.device)
+
+    def __call__(self, pred_y, pred_dy, data, row_mask=None, num_graphs=None):
+        loss = super().__call__(pred_y, pred_dy, data, row_mask=row_mask, num_graphs=num_graphs)
+        self.meters.fold(self.stats, loss, pred_y.shape[0] if num_graphs is None else num_graphs)
+        return loss
+
+
+class IS2RSMeteredLoss(IS2RSLoss):
+    """An is2rs.IS2RSLoss that folds every call's stats and its returned loss into `.meters` (RunningMeters of IS2RS_METERS),
+    as DeNSMeteredLoss does."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.meters = RunningMeters(IS2RS_METERS, self.stats.device)
+
+    def __call__(self, pred_y, pred_pos, data, row_mask=None, num_graphs=None):
+        loss = super().__call__(pred_y, pred_pos, data, row_mask=row_mask, num_graphs=num_graphs)
+        self.meters.fold(self.stats, loss)
+        return loss
+
+
+def dens_train_step(model, optimizer, radius, denoising_pos_std, prob, energy_weight, force_weight, denoising_pos_weight,
+                    corrupt_ratio=None, task_mean=None, task_std=None, seed=0, **bucket_kwargs):
+    """The dens.DeNSTrainStep of `train_one_epoch_dens`, its loss a DeNSMeteredLoss (keep the step between epochs: its graphs
+    are reused).  denoising_pos_std / prob / corrupt_ratio: the driver's --denoising-pos-std / -prob / --denoising-corrupt-ratio
+    (the corruption's std is the loss's); the weights: --energy-weight, --force-weight, --denoising-pos-weight (the loop
+    writes the decayed denoising weight); task_mean / task_std default to the model's.  bucket_kwargs: those of
+    BucketedTrainStep.  A reducer is refused."""
+    _refuse_reducer(optimizer, "dens_train_step")
+    dev = next(model.parameters()).device
+    task_mean = getattr(model, "task_mean", None) if task_mean is None else task_mean
+    task_std = getattr(model, "task_std", None) if task_std is None else task_std
+    if task_mean is None or task_std is None:
+        raise ValueError("dens_train_step: the model carries no task_mean / task_std; pass them")
+    loss = DeNSMeteredLoss(task_mean, task_std, denoising_pos_std, energy_weight, force_weight, denoising_pos_weight, device=dev)
+    step = DeNSTrainStep(model, optimizer, loss, radius, denoising_pos_std, prob, corrupt_ratio, seed=seed, **bucket_kwargs)
+    step.optimizer = optimizer
+    return step
+
+
+def is2rs_train_step(model, optimizer, radius, max_num_neighbors, target_mean, target_std, positions_mean, positions_std,
+                     auxiliary_task_weight, energy_weight=1.0, threshold=0.02, interpolate=True, seed=0, **bucket_kwargs):
+    """The is2rs.IS2RSTrainStep of `train_one_epoch_is2rs`, its loss an IS2RSMeteredLoss, built with total_steps=None: the loop
+    writes the decayed auxiliary weight.  auxiliary_task_weight: the trainer's w0 (`.w0` of the step); `.lr_initial`: the
+    optimizer's lr at construction.  bucket_kwargs: those of BucketedTrainStep (edges="batch" among them).  A reducer and a model
+    without the auxiliary head (use_auxiliary_task=True) are refused."""
+    _refuse_reducer(optimizer, "is2rs_train_step")
+    if not getattr(model, "use_auxiliary_task", False):
+        raise ValueError("is2rs_train_step: the model has no IS2RS head (use_auxiliary_task=True); train it with oc20_train_step")
+    dev = next(model.parameters()).device
+    loss = IS2RSMeteredLoss(target_mean, target_std, positions_mean, positions_std, auxiliary_task_weight,
+                            energy_weight=energy_weight, threshold=threshold, device=dev)
+    step = IS2RSTrainStep(model, optimizer, loss, radius, max_num_neighbors, interpolate=interpolate, seed=seed, total_steps=None,
+                          auxiliary_task_weight=float(auxiliary_task_weight), **bucket_kwargs)
+    step.optimizer = optimizer
+    step.lr_initial = float(optimizer.param_groups[0]["lr"])
+    return step
+
+
+def _check_metered(step, cls, loss_cls, name):
+    if not isinstance(step, cls) or not isinstance(getattr(step, "loss", None), loss_cls):
+        raise ValueError("train_one_epoch_%s needs the step of %s_train_step" % (name, name))
+
+
+def _metered_epoch(step, loader, before, due, line, log):
+    """reset, one step per batch, a read-back per log line and one at the end; returns the averages"""
+    step.model.train()
+    meters = step.loss.meters
+    meters.reset()
+    length = len(loader) if hasattr(loader, "__len__") else None
+    start = time.perf_counter()
+    for k, batch in enumerate(loader):
+        before(k)
+        step.step(batch)
+        if log is not None and due(k, length):
+            log(line(k, length, meters.averages(), 1e3 * (time.perf_counter() - start) / (k + 1)))
+    return meters.averages()
+
+
+def train_one_epoch_dens(step, loader, epoch, epochs, denoising_pos_weight, linear_decay=False, print_freq=100, log=None):
+    """(mae_metrics, loss_metrics) of main_md17_dens.train_one_epoch [ref: main_md17_dens.py:349-450], each {"energy", "force",
+    "denoising_pos"} of evaluate.Average: the losses (L2MAE on the normalised targets) weighted by the molecules, the
+    uncorrupted and the corrupted atoms of each step, the MAEs in real units (forces and noise averaged over x, y, z) likewise.
+    A step without uncorrupted (corrupted) atoms leaves the force (denoising) meters as they are; a meter that never moved
+    has count 0 and avg NaN.  Before the epoch the denoising weight `dens_denoising_pos_weight(denoising_pos_weight, epoch,
+    epochs, linear_decay)` goes to the loss's device word (:372-377).  step: dens_train_step(...); loader: batch mappings with
+    pos, z, batch, y, dy[, num_graphs] on the model's device; log: a callable taking one line, called at step k when
+    k % print_freq == 0 and at the last step."""
+    _check_metered(step, DeNSTrainStep, DeNSMeteredLoss, "dens")
+    w = dens_denoising_pos_weight(denoising_pos_weight, epoch, epochs, linear_decay)
+    step.loss.set_weights(denoising_pos_weight=w)
+
+    def line(k, length, a, ms):
+        return ("Epoch: [%d][%d/%s] \tloss_e: %.5f, loss_f: %.5f, loss_denoising_pos: %.5f, e_MAE: %.5f, f_MAE: %.5f, "
+                "denoising_pos_MAE: %.5f, time/step=%.0fms, lr=%.2e, denoising_pos_weight=%.2e"
+                % (epoch, k, length if length is not None else "?", a["loss_energy"].avg, a["loss_force"].avg,
+                   a["loss_denoising_pos"].avg, a["mae_energy"].avg, a["mae_force"].avg, a["mae_denoising_pos"].avg, ms,
+                   step.optimizer.param_groups[0]["lr"], w))
+    a = _metered_epoch(step, loader, lambda k: None, lambda k, n: k % print_freq == 0 or (n is not None and k == n - 1),
+                       line, log)
+    parts = ("energy", "force", "denoising_pos")
+    return {p: a["mae_" + p] for p in parts}, {p: a["loss_" + p] for p in parts}
+
+
+def train_one_epoch_is2rs(step, loader, lr_lambda=None, total_steps=None, auxiliary_task_weight=None, print_freq=100, log=None,
+                          lr_initial=None):
+    """{name: evaluate.Average} of IS2RS_METERS for one epoch of the IS2RE + IS2RS trainer [ref: energy_trainer_v2.py:240-317]:
+    "loss" (the returned total), "energy_mae", "energy_mse", "energy_within_threshold" -- each the plain mean of the steps'
+    figures, as avg_metric_dict keeps them -- and "pos_mae", weighted by the free atoms.  Before step k of the instance
+    (`step.steps`, counted over epochs) the loop writes param_group["lr"] = lr_initial * lr_lambda(k) (as train_one_epoch_oc20;
+    lr_initial: the step's `.lr_initial` by default) and, with total_steps, the auxiliary weight
+    is2rs.auxiliary_task_weight(w0, k + 1, total_steps) (the reference's self.step is 1-based, :254, :468; w0: the step's
+    `.w0` by default).  step: is2rs_train_step(...) -- a step that schedules the weight itself (total_steps set) is refused.
+    log: a callable taking one line, called when the 1-based step is a multiple of print_freq, and at the epoch's first and
+    last step (:296-317); the line holds the running averages, not the step's own figures."""
+    _check_metered(step, IS2RSTrainStep, IS2RSMeteredLoss, "is2rs")
+    if step.total_steps is not None:
+        raise ValueError("train_one_epoch_is2rs: the step decays the auxiliary weight itself (total_steps=%d); build it with "
+                         "is2rs_train_step (total_steps=None): the loop owns the schedule" % step.total_steps)
+    lr0 = float(lr_initial if lr_initial is not None else getattr(step, "lr_initial", step.optimizer.param_groups[0]["lr"]))
+    w0 = step.w0 if auxiliary_task_weight is None else auxiliary_task_weight
+    if total_steps is not None and w0 is None:
+        raise ValueError("train_one_epoch_is2rs: no auxiliary_task_weight to decay")
+    aux = [float(step.loss._w_host[1])]
+
+    def before(k):
+        if lr_lambda is not None:
+            lr = lr0 * lr_lambda(step.steps)
+            for g in step.optimizer.param_groups:
+                g["lr"] = lr
+        if total_steps is not None:
+            aux[0] = is2rs.auxiliary_task_weight(w0, step.steps + 1, total_steps)
+            step.loss.set_weights(auxiliary_task_weight=aux[0])
+
+    def line(k, length, a, ms):
+        parts = ["%s: %.2e" % (n, a[n].avg) for n in ("energy_mae", "energy_mse", "energy_within_threshold", "loss")]
+        parts += ["lr: %.2e" % step.optimizer.param_groups[0]["lr"], "step: %d" % step.steps, "aux_weight: %.2e" % aux[0]]
+        return ", ".join(parts)
+    return _metered_epoch(step, loader, before,
+                          lambda k, n: step.steps % print_freq == 0 or k == 0 or (n is not None and k == n - 1), line, log)
+
+
 # --------------------------------------------------------------------------------------------------------------------- schedules
 def lr_lambda_cosine(step, warmup, warmup_factor, total, lr_min_factor):
     """The OC20 trainer's per-step cosine factor [ref: oc20/trainer/lr_scheduler.py:20-34 cosine_lr_lambda]: a linear warm-up
@@ -317,6 +547,15 @@ def lr_lambda_multistep(step, warmup, warmup_factor, decay_steps, decay_rate):
         alpha = step / float(warmup)
         return warmup_factor * (1.0 - alpha) + alpha
     return pow(decay_rate, sum(1 for m in decay_steps if m <= step))
+
+
+def dens_denoising_pos_weight(denoising_pos_weight, epoch, epochs, linear_decay=True):
+    """The denoising weight of epoch `epoch` (from 0) [ref: main_md17_dens.py:372-377]: with --use-denoising-pos-weight-linear-
+    decay w (1 - min(1, epoch / epochs)), a linear decay to 0 over the run; otherwise w."""
+    w = float(denoising_pos_weight)
+    if not linear_decay:
+        return w
+    return w * (1 - min(1.0, ((epoch + 0.0) / epochs)))
 
 
 def cosine_epoch_lr(epoch, lr, epochs, warmup_epochs=0, warmup_lr=1e-6, min_lr=1e-5):

@@ -861,6 +861,28 @@ int eqf_ef_loss_bwd(const float* d_loss, const float* pred_y, const float* y, in
                     const float* pred_dy, const float* dy, const float* row_mask, int N, const float* weights, int criterion,
                     double task_mean, double task_std, float* d_pred_y, float* d_pred_dy, void* stream);
 
+/* The running meters of the DeNS and IS2RE + IS2RS training loops: one step's means folded into fp64 (sum, count) pairs, one
+ * launch.  [ref: engine.py:23-27 AverageMeter.update(val, n): sum += val n, count += n; main_md17_dens.py:361-427 (three loss
+ * and three MAE meters, each weighted by a per-step count, skipped when `loss_f.isnan()`); energy_trainer_v2.py:247-317
+ * (avg_metric_dict: one update per step, weight 1)]  For meter i < M (1 <= M <= EQF_METERS_MAX):
+ *   v_i = value_index[i] >= 0 ? stats[value_index[i]] : loss[0]                 (value_index[i] == -1: the loss scalar)
+ *   w_i = weight_index[i] >= 0 ? stats[weight_index[i]] : weight_const[i]      (weight_index[i] == -1: the constant)
+ *   w_i == 0:   acc[2i], acc[2i + 1] untouched and v_i not read (a NaN mean of an empty set reaches nothing)
+ *   otherwise:  acc[2i] += (double)v_i (double)w_i,   acc[2i + 1] += (double)w_i
+ * stats [n_stats] fp32 and loss [1] fp32 are device memory (the stats buffer and the returned scalar of a loss); acc [2 M] fp64,
+ * device memory, is only added to (clear it with a fill on the same stream).  value_index, weight_index and weight_const [M]
+ * are HOST arrays, read before this returns and copied into the launch: a captured launch keeps the values it was built
+ * with.  A constant weight must be an integer in [0, 2^29) (the graph count of the step, or 1): an fp32 value times it, or
+ * times an fp32 count from stats, is exact in fp64, so the sums depend only on the order of the additions and equal the
+ * host's AverageMeter fed the same fp32 values bit for bit.  Argument errors, refused before anything is launched: M outside
+ * [1, EQF_METERS_MAX], a missing acc / value_index / weight_index, an index below -1 or >= n_stats, stats missing where an
+ * index reads it, loss missing where a value is the loss, weight_const missing where a weight is constant, and a constant
+ * weight that is not such an integer.  One workgroup of one wave, lane i owns meter i: no atomics, no workspace, the same
+ * bits on every run.  Enqueue-only: legal inside a stream capture.  Launches that share acc must be ordered (one stream). */
+#define EQF_METERS_MAX 16
+int eqf_meter_fold(const float* stats, int n_stats, const float* loss, int M, const int* value_index,
+                   const int* weight_index, const double* weight_const, double* acc, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; used by bench.py for the roofline line)
  * ------------------------------------------------------------------------------------------- */
