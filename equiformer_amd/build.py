@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libequiformer_hip.so")
-SOURCES = ["gemm.hip", "gemmx.hip", "sfc.hip", "sfcx.hip", "sfcy.hip", "sfcw.hip", "rowops.hip", "graphnorm.hip", "edge.hip", "dropout.hip", "edgedeg.hip", "graph.hip", "second.hip", "dpattn.hip", "optim.hip", "dens.hip", "is2rs.hip", "metrics.hip", "trainloss.hip", "meters.hip", "prof.hip"]
+SOURCES = ["gemm.hip", "gemmx.hip", "sfc.hip", "sfcx.hip", "sfcy.hip", "sfcw.hip", "rowops.hip", "graphnorm.hip", "edge.hip", "dropout.hip", "edgedeg.hip", "graph.hip", "second.hip", "dpattn.hip", "optim.hip", "dens.hip", "is2rs.hip", "metrics.hip", "trainloss.hip", "meters.hip", "predict.hip", "prof.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 # per-source flags.  sfcx.hip issues bf16 MFMAs: no packed-FP32 VALU instruction may be generated beside them (the SLP
 # vectoriser is what turns neighbouring scalar fp32 operations into v_pk_*_f32)

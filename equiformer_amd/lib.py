@@ -191,6 +191,7 @@ SIGNATURES = {
     "eqf_ef_loss_fwd": [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, _d, _d, _d, c_fp, c_fp, c_fp],
     "eqf_ef_loss_bwd": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, _d, _d, c_fp, c_fp, c_fp],
     "eqf_meter_fold": [c_fp, c_int, c_fp, c_int, _P_INT, _P_INT, _P_DBL, c_fp, c_fp],
+    "eqf_predict_append": [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, _f, _f, _f, _f, _f, _f, _f, _f, c_fp, c_fp],
     "eqf_prof_enable": [ctypes.c_char_p],
     "eqf_prof_report": [ctypes.c_char_p, c_int],
 }

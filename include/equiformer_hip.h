@@ -883,6 +883,49 @@ int eqf_ef_loss_bwd(const float* d_loss, const float* pred_y, const float* y, in
 int eqf_meter_fold(const float* stats, int n_stats, const float* loss, int M, const int* value_index,
                    const int* weight_index, const double* weight_const, double* acc, void* stream);
 
+/* The OC20 prediction pass: one batch's denormalised energies, ids, atom counts and (write_pos) predicted relaxed positions
+ * appended to result buffers on the device, one launch.  [ref: oc20/trainer/energy_trainer_v2.py:170-204 predict: the target
+ * normalizer's denorm, `predictions["id"].extend(sid.tolist())`, `predictions["energy"].extend(out["energy"].tolist())`, and
+ * under write_pos `pred_pos[tag_mask] = pred_pos[tag_mask] + delta_pos[tag_mask]` split by natoms -- `.tolist()` / `.cpu()` read-backs
+ * per batch]
+ * desc [EQF_PREDICT_DESC_WORDS] int64, DEVICE memory, describes the sink: the cursors gc = desc[GRAPH_CURSOR] and
+ * ac = desc[ATOM_CURSOR], the capacities desc[GRAPH_CAP] (structures) and desc[ATOM_CAP] (atoms), two counters of what was
+ * dropped, and the device addresses of energy_out (fp32 [GRAPH_CAP]), sid_out (int64 [GRAPH_CAP]), natoms_out (int32
+ * [GRAPH_CAP]) and pos_out (fp32 [ATOM_CAP, 3]).  With r0 = mol_ptr[0] and n = mol_ptr[B] - r0 the launch writes, for b < B
+ * and the rows r0 <= i < mol_ptr[B]:
+ *   energy_out[gc + b] = fl(fl(energy[b] target_std) + target_mean)      sid_out[gc + b] = sid[b]
+ *   natoms_out[gc + b] = mol_ptr[b + 1] - mol_ptr[b]
+ *   pos_out[ac + i - r0][c] = tags[i] > 0 ? fl(pos[i][c] + fl(fl(delta[i][c] pos_std_c) + pos_mean_c)) : pos[i][c] (its bits)
+ * and then advances the cursors IN desc: gc += B, ac += n.  Every operation is a separately rounded fp32 one, in the order
+ * written: the results are eager torch's bit for bit.  energy holds at least B floats ([rows] or [rows, 1] of a padded batch),
+ * sid B int64, mol_ptr B + 1 int32; pos / delta are [>= mol_ptr[B], 3] fp32, tags as eqf_is2rs_perturb.  The phantom structure's
+ * row and the rows >= mol_ptr[B] are never read.  pos == NULL (then delta and tags are NULL too): the atom part and the atom
+ * cursor are left alone.  The normalisation constants travel by value: configuration, which a captured launch may freeze.
+ * A batch is taken whole or not at all: when gc + B > GRAPH_CAP or (with pos) ac + n > ATOM_CAP nothing is written, the cursors
+ * stay, and DROPPED_GRAPHS += B, DROPPED_ATOMS += n (0 without pos); nothing is ever written past a capacity.  Because cursors,
+ * capacities and addresses are read from desc when the launch RUNS, a launch captured in a HIP graph appends behind whatever
+ * ran before each replay, and sees buffers the host has replaced (grown) between two replays.
+ * Argument errors, refused before anything is launched: a missing energy / sid / mol_ptr / desc, B < 0, delta or tags without
+ * pos, pos without delta and tags.  B == 0 returns 0 without a launch.  One workgroup of EQF_PREDICT_THREADS lanes,
+ * lane-strided copies, then one thread advances the cursors: no atomics, no workspace.  Enqueue-only: legal inside a stream
+ * capture.  Launches that share desc must be ordered (one stream), as must the host's writes to it. */
+#define EQF_PREDICT_THREADS 256
+#define EQF_PREDICT_DESC_WORDS 10
+#define EQF_PREDICT_GRAPH_CURSOR 0
+#define EQF_PREDICT_ATOM_CURSOR 1
+#define EQF_PREDICT_GRAPH_CAP 2
+#define EQF_PREDICT_ATOM_CAP 3
+#define EQF_PREDICT_DROPPED_GRAPHS 4
+#define EQF_PREDICT_DROPPED_ATOMS 5
+#define EQF_PREDICT_ENERGY_OUT 6
+#define EQF_PREDICT_SID_OUT 7
+#define EQF_PREDICT_NATOMS_OUT 8
+#define EQF_PREDICT_POS_OUT 9
+int eqf_predict_append(const float* energy, const long long* sid, const int* mol_ptr, int B, const float* pos,
+                       const float* delta, const void* tags, int tags_is64, float target_mean, float target_std,
+                       float pos_mean_x, float pos_mean_y, float pos_mean_z, float pos_std_x, float pos_std_y,
+                       float pos_std_z, long long* desc, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; used by bench.py for the roofline line)
  * ------------------------------------------------------------------------------------------- */
