@@ -100,20 +100,26 @@ def ragged_graph(degrees, n_src, seed, device="cpu"):
 def evaluate(fn, inputs, grad_outputs, dtype, device="cpu", wrt=None):
     """(outputs, gradients) of fn at `inputs` (float64 CPU tensors; integer tensors and non-tensors pass through) in
     `dtype` on `device`; `grad_outputs` are the cotangents, one per output; gradients are taken wrt the floating inputs
-    listed in `wrt` (default: all of them)."""
+    listed in `wrt` (default: all of them).  On a GPU every tensor the function receives, cotangents included, is a copy
+    between guard bands (tests/poison.py: NaN around floating tensors, so that a load past the end shows in the result;
+    index tensors keep valid contents); the floating inputs are leaves as before."""
+    on_gpu = torch.device(device).type != "cpu"
+    if on_gpu:
+        from poison import guard_input
+    put = (lambda t: guard_input(t.to(device))) if on_gpu else (lambda t: t.to(device))
     ins = []
     for t in inputs:
         if torch.is_tensor(t) and t.is_floating_point():
-            ins.append(t.detach().to(dtype).to(device).requires_grad_(True))
+            ins.append(put(t.detach().to(dtype)).requires_grad_(True))
         elif torch.is_tensor(t):
-            ins.append(t.to(device))
+            ins.append(put(t))
         else:
             ins.append(t)
     outs = fn(*ins)
     outs = list(outs) if isinstance(outs, (tuple, list)) else [outs]
     fl = [i for i, t in enumerate(ins) if torch.is_tensor(t) and t.is_floating_point()]
     wrt = fl if wrt is None else wrt
-    gos = [g.to(dtype).to(device) for g in grad_outputs]
+    gos = [put(g.to(dtype)) for g in grad_outputs]
     grads = torch.autograd.grad(outs, [ins[i] for i in wrt], gos, allow_unused=True)
     return [o.detach() for o in outs], list(grads)
 

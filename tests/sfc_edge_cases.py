@@ -20,7 +20,9 @@ Guarded buffers.  Every per-edge tensor of a launch sits in the middle of a [G +
 largest tile: an over-read inside a tile stays inside the allocation).  Guard rows of inputs are NaN (a padded row that
 reaches a result through a product with a zero mask shows), guard rows of outputs are NaN (overwritten outputs) or a recorded
 random sentinel (accumulated outputs: an atomic add into a NaN would leave the NaN); `check_guarded` compares the guard
-rows bit for bit with what was put there.  Flat parameter gradients are guarded as [n / 32, 32] rows.
+rows bit for bit with what was put there.  Flat parameter gradients are guarded as [n / 32, 32] rows.  On a GPU the whole
+buffer is a `poison.guard_input` copy: bands of tests/poison.py around the guard rows, checked by the `poisoned_ops` fixture
+where a test uses it (a store further out than G rows).
 
 Metric and bounds: those of the sibling files (largest error over the largest reference entry of the tensor; split 1e-4,
 bf16 3e-2, split6 and exact fp32 max(5e-6, 4 x float32 yardstick on the same inputs), bias gradients 1e-5)."""
@@ -39,6 +41,7 @@ import fp64_ops  # noqa: E402
 from fp64_tp import blocks as _blocks, reference  # noqa: E402
 from equiformer_amd import lib as _lib, ops, so3  # noqa: E402
 from equiformer_amd.layout import DtpTable, RowLayout  # noqa: E402
+from poison import guard_input  # noqa: E402
 
 G = 128
 E_TILE = [1, 31, 32, 33, 63, 65, 127, 129]
@@ -231,6 +234,8 @@ class Guarded:
     what the middle held before the launch (accumulated outputs) or None"""
 
     def __init__(self, buf, rows, prefill):
+        if buf.device.type != "cpu":  # the whole buffer once more between the bands of tests/poison.py: a store further out than G rows
+            buf = guard_input(buf)
         self.buf, self.rows, self.prefill = buf, rows, prefill
         self.mid = buf[G:G + rows]
         self.guards = self._guard_bits().clone()

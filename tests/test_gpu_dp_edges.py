@@ -27,6 +27,8 @@ restatement on the same inputs ("-": plain bound):
                    dq 4.13e-07; dkv 5.27e-08 (H = 3)
   G = 257          backward dq and dk inside 1e-05 on the chain of 5 edges; the forward returns EQF_E_UNSUPPORTED
 Wall time: 63 tests in 4.8 s; the slowest item 1.2 s (the first of the file: library load and context), every other <= 0.14 s.
+Wall time of this file on an MI355X, one run each (pytest's figure): 4.5 s at the parent commit, 4.4 s with every allocation
+of the opted-in tests poisoned and guarded (tests/poison.py).
 """
 import ctypes
 import os
@@ -40,8 +42,9 @@ import dp_edge_cases as dpc  # noqa: E402
 import fp64_ops as fo  # noqa: E402
 from sfc_edge_cases import check_guarded, guarded  # noqa: E402
 from test_gpu_op_edges import _Checker, _dev  # noqa: E402
+from poison import poisoned_ops  # noqa: E402,F401  (every launch of this file runs on poisoned, guarded allocations)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_ops")]
 
 
 def _setup(head_irr, H, kind):

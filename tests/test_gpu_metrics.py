@@ -4,9 +4,12 @@ Bounds.  The kernel and the restatement form every term in fp64 from the same fp
 the summation (and an fma the compiler may contract).  A sum of n non-negative fp64 terms is within n 2^-53 relative of the exact
 sum in any order; the largest sum here has 3 (4 W + 3) = 3 081 < 10^4 terms: 10^4 2^-53 < 1.2e-12, so the bound is 1e-12 relative.
 Counts (graphs, atoms, errors under the threshold) are exact: the targets are drawn so that no |e| of the restatement lies
-within 1e-9 of the threshold (asserted), twelve orders of magnitude above what the two sides can differ by."""
+within 1e-9 of the threshold (asserted), twelve orders of magnitude above what the two sides can differ by.
+Wall time of this file on an MI355X, one run each (pytest's figure): 2.5 s at the parent commit, 2.4 s with every allocation
+of the opted-in tests poisoned and guarded (tests/poison.py)."""
 import pytest
 import torch
+from poison import guard_input, poisoned_ops  # noqa: E402,F401  (the fixture of the tests that run on poisoned, guarded allocations)
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +69,7 @@ def _run(meter, pred_y, y, n_graphs, pred_dy=None, dy=None, mask=None, reset=Tru
     dev = _dev()
     if reset:
         meter.reset()
-    mv = lambda t: None if t is None else t.to(dev)  # noqa: E731
+    mv = lambda t: None if t is None else guard_input(t.to(dev))  # noqa: E731  (NaN right behind the last row: tests/poison.py)
     meter.update(mv(pred_y), mv(y), n_graphs, mv(pred_dy), mv(dy), mv(mask))
     return meter.acc.clone()
 
@@ -79,6 +82,7 @@ def meter():
     return Meter(MEAN, STD, THR, device=_dev())
 
 
+@pytest.mark.usefixtures("poisoned_ops")
 @pytest.mark.parametrize("n_graphs", GRAPHS)
 def test_sums_against_fp64_at_every_size(meter, n_graphs):
     """every n_graphs x N, with and without forces, with and without a mask; rows = n_graphs + 1"""
@@ -115,6 +119,7 @@ def test_a_mask_without_forces_and_energies_of_other_shapes_and_dtypes(meter):
         meter.update(pred_y.to(_dev()), y.to(_dev()), 67)  # more graphs than rows
 
 
+@pytest.mark.usefixtures("poisoned_ops")
 @pytest.mark.parametrize("n_graphs,N", [(1, 1), (65, W + 1), (W + 1, 4 * W + 3)])
 def test_nan_and_inf_in_excluded_rows_change_no_bit(meter, n_graphs, N):
     pred_y, y, pred_dy, dy, mask = _case(n_graphs, N, seed=7 + N)

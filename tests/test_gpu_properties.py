@@ -1,11 +1,14 @@
 """Size-independent properties of the HIP path at BASELINE.json's full sizes (where the CPU oracle would take minutes),
-and the degenerate inputs: molecules without edges, a batch without any edge."""
+and the degenerate inputs: molecules without edges, a batch without any edge.
+Wall time of this file on an MI355X, one run each (pytest's figure): 3.7 s at the parent commit, 3.8 s with every allocation
+of the opted-in tests poisoned and guarded (tests/poison.py)."""
 import math
 
 import pytest
 import torch
 
 from oracle import nets as onets
+from poison import poisoned_model  # noqa: E402,F401  (the fixture of the tests that run on poisoned, guarded allocations)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +75,7 @@ def test_md17_forces_equivariant_and_sum_to_zero():
     assert float(net.abs().max()) < 1e-4 * float(F.abs().max()) * math.sqrt(21)
 
 
+@pytest.mark.usefixtures("poisoned_model")
 def test_molecules_without_edges_and_empty_graph():
     """A single-atom molecule and a far-apart pair have no edges: their energy comes from the embeddings alone and
     must equal the oracle's; a batch in which NO molecule has an edge (E = 0 everywhere on the path) runs as well."""

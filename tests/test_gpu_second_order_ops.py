@@ -32,6 +32,8 @@ quantity; this module writes such a file when EQF_SECOND_ORDER_ERRORS names one)
     sep_fctp_gated  split 8.7e-6 (L / weight)       bf16 5.8e-3 (L / x_raw, E(3) gate)
     linears         fp32 7.2e-7 (d W, irreps_linear)   split 1.4e-5 (L / W, 8x0e+4x1e -> 8x0e+4x1e+4x2e; bar 8e-5)
     dtp, coupling   2.5e-7          fold, gather_add, segment_scale, add_layer_norm   3.6e-7          edge_geometry, periodic   4.9e-7
+Wall time of this file on an MI355X, one run each (pytest's figure): 4.9 s at the parent commit, 7.7 s with every allocation
+of the opted-in tests poisoned and guarded (tests/poison.py).
 """
 import os
 import sys
@@ -49,8 +51,9 @@ import second_order_ref as so  # noqa: E402
 from second_order_ref import TOL, _compare, _dev, _rel  # noqa: E402
 from equiformer_amd import ops  # noqa: E402
 from equiformer_amd.layout import RowLayout  # noqa: E402
+from poison import poisoned_ops  # noqa: E402,F401  (every launch of this file runs on poisoned, guarded allocations)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_ops")]
 
 LIN_TOL = {"fp32": 1.0, "split": 4.0}  # tests/test_gpu_ops.py::MODE_TOL
 _worst = {}   # (operator, mode, quantity) -> worst error of this run

@@ -8,7 +8,9 @@ difference is exactly zero; NaN in every phantom row and in the energy row past 
 Bound: 1e-6 relative to the largest magnitude of the quantity -- the bound at which tests/test_gpu_dens_step.py holds
 eqf_dens_loss_* to tests/fp64_dens.py; the summation scheme is the same (fp64 lane partials, wave shuffles, waves in order),
 so the error is the final fp32 store (2^-24) plus fp64 rounding.  The worst measured figure is printed; on an MI355X: loss
-5.4e-8, d_pred_y 5.7e-8, d_pred_dy 4.8e-8, the ten sums 3.3e-16."""
+5.4e-8, d_pred_y 5.7e-8, d_pred_dy 4.8e-8, the ten sums 3.3e-16.
+Wall time of this file on an MI355X, one run each (pytest's figure): 3.5 s at the parent commit, 3.9 s with every allocation
+of the opted-in tests poisoned and guarded (tests/poison.py)."""
 import ctypes
 import math
 import os
@@ -21,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fp64_trainloss as ft  # noqa: E402
+from poison import guard_input, poisoned_ops  # noqa: E402,F401  (the fixture of the tests that run on poisoned, guarded allocations)
 
 DEV = torch.device("cuda:0")
 BOUND = 1e-6
@@ -43,7 +46,7 @@ class Buf:
         self.shape, self.n, self.dtype = tuple(data.shape), flat.numel(), dtype
         buf = torch.full((2 * G + self.n,), float("nan"), dtype=dtype)
         buf[G:G + self.n] = flat
-        self.buf = buf.to(DEV)
+        self.buf = guard_input(buf.to(DEV))  # (and the whole of it between the bands of tests/poison.py: a store further out than G)
         self.guards = self._guard_bits().clone()
 
     def _guard_bits(self):
@@ -151,6 +154,7 @@ def _close(got, want, what, key):
     assert err <= BOUND * scale, (what, key, err, scale)
 
 
+@pytest.mark.usefixtures("poisoned_ops")
 @pytest.mark.parametrize("forces", [True, False])
 @pytest.mark.parametrize("crit", ["l1", "l2", "l2mae"])
 def test_grid_against_fp64(crit, forces):
@@ -183,6 +187,7 @@ def test_grid_against_fp64(crit, forces):
         print("%-20s worst %.3e at %s (bound %.0e)" % (what, rel, key, BOUND))
 
 
+@pytest.mark.usefixtures("poisoned_ops")
 def test_sums_accumulate_over_three_batches():
     prefill = torch.randn(10, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
     acc, want = prefill, prefill.clone()
@@ -195,6 +200,7 @@ def test_sums_accumulate_over_three_batches():
     print("accumulated sums: worst %.3e" % max(v[0] for k, v in WORST.items() if k.startswith("accumulated")))
 
 
+@pytest.mark.usefixtures("poisoned_ops")
 def test_operator_autograd_and_device_weights():
     """ops.ef_loss / EFLoss: the autograd path, the meter's sums, a weight changed between two calls"""
     from equiformer_amd.train import EFLoss
