@@ -26,6 +26,45 @@ __global__ __launch_bounds__(256) void gather_add_kernel(const float* __restrict
   reinterpret_cast<float4*>(msg)[idx] = v;
 }
 
+// Rows of at least GATHER_ROW_MIN_D4 float4 columns (QM9: 120).  The kernel above pays, per float4, a 64-bit division and
+// two dependent round trips (src[e] / dst[e], then the node rows).  Here a wavefront owns GATHER_ROWS consecutive edges: the
+// edge index is wave-uniform (readfirstlane), so the index loads of all its edges go out together on the scalar unit, and the
+// lanes stride the float4 columns with the 2 x GATHER_ROWS row loads of a column step requested before the first is used.
+// Edges past E are clamped to E - 1 and not stored.  msg = a[src] + b[dst], the same single add per element.
+constexpr int GATHER_ROW_MIN_D4 = 32;
+constexpr int GATHER_WAVES = 4, GATHER_ROWS = 4;
+
+__global__ __launch_bounds__(64 * GATHER_WAVES) void gather_add_rows_kernel(
+    const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ src, const int* __restrict__ dst,
+    float* __restrict__ msg, int E, int D4) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)(threadIdx.x & 63);
+  const int e0 = ((int)blockIdx.x * GATHER_WAVES + wave) * GATHER_ROWS;
+  if (e0 >= E) return;
+  const float4* ra[GATHER_ROWS];
+  const float4* rb[GATHER_ROWS];
+#pragma unroll
+  for (int j = 0; j < GATHER_ROWS; ++j) {
+    const int e = min(e0 + j, E - 1);
+    ra[j] = reinterpret_cast<const float4*>(a) + (long)src[e] * D4;
+    rb[j] = b ? reinterpret_cast<const float4*>(b) + (long)dst[e] * D4 : nullptr;
+  }
+  for (int c = lane; c < D4; c += 64) {
+    float4 v[GATHER_ROWS], w[GATHER_ROWS];
+#pragma unroll
+    for (int j = 0; j < GATHER_ROWS; ++j) v[j] = ra[j][c];
+    if (b) {
+#pragma unroll
+      for (int j = 0; j < GATHER_ROWS; ++j) w[j] = rb[j][c];
+#pragma unroll
+      for (int j = 0; j < GATHER_ROWS; ++j) v[j].x += w[j].x, v[j].y += w[j].y, v[j].z += w[j].z, v[j].w += w[j].w;
+    }
+#pragma unroll
+    for (int j = 0; j < GATHER_ROWS; ++j)
+      if (e0 + j < E) reinterpret_cast<float4*>(msg)[(long)(e0 + j) * D4 + c] = v[j];
+  }
+}
+
 // segment n of one segmented sum; one workgroup of 128
 __device__ __forceinline__ void segment_sum_block(const float* __restrict__ x, const int* __restrict__ ptr,
                                                   const int* __restrict__ perm, float* __restrict__ out, int D,
@@ -282,20 +321,36 @@ __device__ __forceinline__ float dslrelu(float x) {
   return 0.6f + 0.4f * (2.f * s - 1.f) + 0.8f * x * s * (1.f - s);
 }
 
-// Kh in {8,16,32,64}: Kh consecutive lanes share (edge, head)
+// Kh in {8,16,32,64}: Kh consecutive lanes share (edge, head).  A thread takes ALPHA_U elements 256 apart, all requested before
+// the first is used; the 64-bit division idx / HK is done once per workgroup (on its first index, wave-uniform), a lane divides
+// only its small offset from there.  Every (edge, head) is still summed by the same Kh lanes with the same butterfly.
+constexpr int ALPHA_U = 4;
+
 __global__ __launch_bounds__(256) void alpha_fwd_kernel(const float* __restrict__ a, const float* __restrict__ adot,
                                                         float* __restrict__ logit, long total, int HK, int Kh, float c) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  float v = 0.f;
-  long e = 0;
-  int col = 0;
-  if (idx < total) {
-    e = idx / HK;
-    col = (int)(idx - e * HK);
-    v = c * slrelu(a[idx]) * adot[col];
+  const long base = (long)blockIdx.x * (256 * ALPHA_U);
+  const long eb = base / HK;
+  const unsigned r0 = (unsigned)(base - eb * HK) + threadIdx.x;  // < HK + 256
+  const int sh = __builtin_ctz((unsigned)Kh);
+  float av[ALPHA_U], dv[ALPHA_U];
+  long e[ALPHA_U];
+  int col[ALPHA_U];
+#pragma unroll
+  for (int u = 0; u < ALPHA_U; ++u) {
+    const long idx = base + u * 256 + threadIdx.x;
+    const unsigned r = r0 + u * 256, q = r / (unsigned)HK;
+    e[u] = eb + q;
+    col[u] = (int)(r - q * (unsigned)HK);
+    av[u] = idx < total ? a[idx] : 0.f;
+    dv[u] = idx < total ? adot[col[u]] : 0.f;
   }
-  for (int o = Kh >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if (idx < total && (col % Kh) == 0) logit[e * (HK / Kh) + col / Kh] = v;
+#pragma unroll
+  for (int u = 0; u < ALPHA_U; ++u) {
+    const long idx = base + u * 256 + threadIdx.x;
+    float v = idx < total ? c * slrelu(av[u]) * dv[u] : 0.f;
+    for (int o = Kh >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (idx < total && (col[u] & (Kh - 1)) == 0) logit[e[u] * (HK >> sh) + (col[u] >> sh)] = v;  // Kh is a power of two
+  }
 }
 
 __global__ __launch_bounds__(256) void alpha_bwd_kernel(const float* __restrict__ a, const float* __restrict__ adot,
@@ -320,8 +375,14 @@ __global__ __launch_bounds__(256) void alpha_bwd_kernel(const float* __restrict_
   atomicAdd(d_adot + col, (float)acc);
 }
 
-// float4 columns, RP edge rows per pass, four passes in flight: the column-per-thread kernel above walks 16 edges in a
-// serial loop with 3 waves per SIMD on the chip -- 47 us for 26 MB.  HK % 4 == 0, HK / 4 <= 256, Kh % 4 == 0.
+// float4 columns, RP = 256 / (HK / 4) edge rows per pass, ALPHA_BWD_U = 4 passes (their a rows and d_logit words) requested
+// before the first is used; a workgroup walks its CH = 64 edges in CH / (4 RP) such steps and ends with one atomic per column:
+// 17.4 us per launch at E = 25 354, HK = 256 (26 MB in, 26 MB out; 397 workgroups, four dependent steps each).  Measured and not
+// kept: all 16 passes of a workgroup in flight (133 VGPRs) took 19.3 us -- the chain is not what bounds this kernel.  Fewer
+// edges per workgroup would multiply the same-address atomics on d_adot, which is what CH = 64 keeps down.
+// HK % 4 == 0, HK / 4 <= 256, Kh % 4 == 0; every other shape takes alpha_bwd_kernel above.
+constexpr int ALPHA_BWD_U = 4;  // passes in flight
+
 __global__ __launch_bounds__(256) void alpha_bwd4_kernel(const float* __restrict__ a, const float* __restrict__ adot,
                                                          const float* __restrict__ d_logit, float* __restrict__ da,
                                                          float* __restrict__ d_adot, int E, int HK, int Kh, float c,
@@ -335,18 +396,18 @@ __global__ __launch_bounds__(256) void alpha_bwd4_kernel(const float* __restrict
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   if (ty < RP) {
     const float4 ad = reinterpret_cast<const float4*>(adot)[tx];
-    for (int eb = e0 + ty; eb < e1; eb += 4 * RP) {
-      float4 av[4];
-      float g[4];
+    for (int eb = e0 + ty; eb < e1; eb += ALPHA_BWD_U * RP) {
+      float4 av[ALPHA_BWD_U];
+      float g[ALPHA_BWD_U];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < ALPHA_BWD_U; ++u) {
         const int e = eb + u * RP;
         const bool ok = e < e1;
         av[u] = ok ? reinterpret_cast<const float4*>(a)[(long)e * Q + tx] : make_float4(0.f, 0.f, 0.f, 0.f);
         g[u] = ok ? d_logit[(long)e * H + h] * c : 0.f;
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < ALPHA_BWD_U; ++u) {
         const int e = eb + u * RP;
         if (e < e1) {
           float4 o;
@@ -394,6 +455,11 @@ __device__ __forceinline__ float keep_scale(unsigned long long seed, unsigned lo
   z = z ^ (z >> 31);
   const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
   return (u >= p) ? 1.f / (1.f - p) : 0.f;
+}
+
+// v of lane `src` (a constant) as a wave-uniform value: v_readlane, no trip through the LDS crossbar
+__device__ __forceinline__ float lane_value(float v, int src) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
 constexpr int MAX_SLOTS = 4;  // up to 256 float4 groups (1024 channels) per head
@@ -499,6 +565,13 @@ __global__ void attn_fwd_half_kernel(const float* __restrict__ logit, const floa
   if (half == 0 && col4 >= 0) reinterpret_cast<float4*>(out)[(long)n * D4 + col4] = acc;
 }
 
+// The backward of attn_fwd_half_kernel, with the same two cuts in its chain of memory round trips: (1) the value rows of the
+// first four edges, the row's d_out and the head's alpha (lane j holding edge beg + j) depend on row_ptr only and are requested
+// together; inside the loop the next four value rows are requested before the current ones are used, and alpha reaches the
+// edge loop by lane shuffles; (2) d(alpha) of the row's first 64 edges stays in registers -- after the half-wave butterfly
+// lanes 0 and 32 hold the figures of the step's four edges, and lane j keeps the one of edge beg + j -- so the softmax
+// fix-up at the end needs no stash in d_logit, no fence and no re-read.  Only edges from the 65th on take the memory stash.
+// Same terms, same order, same butterflies as before: the results are bit-identical.
 __global__ void attn_bwd_half_kernel(const float* __restrict__ alpha, const float* __restrict__ value,
                                      const int* __restrict__ row_ptr, const float* __restrict__ d_out,
                                      float* __restrict__ d_value, float* __restrict__ d_logit, const HeadTab T,
@@ -511,16 +584,29 @@ __global__ void attn_bwd_half_kernel(const float* __restrict__ alpha, const floa
   const int half = lane >> 5, gl = lane & 31;
   const int beg = row_ptr[n], end = row_ptr[n + 1];
   const int H = T.H, D4 = T.D >> 2;
+  const int deg = end - beg;
   const int col4 = (gl < T.G) ? head_col(T, h, gl) >> 2 : -1;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4* const V = reinterpret_cast<const float4*>(value);
+  float4 xa = (beg + half < end && col4 >= 0) ? V[(long)(beg + half) * D4 + col4] : z4;
+  float4 xb = (beg + 2 + half < end && col4 >= 0) ? V[(long)(beg + 2 + half) * D4 + col4] : z4;
+  const float al = lane < deg ? alpha[(long)(beg + lane) * H + h] : 0.f;
   const float4 go = (col4 >= 0) ? reinterpret_cast<const float4*>(d_out)[(long)n * D4 + col4] : z4;
   float s_acc = 0.f;
+  float da_mine = 0.f;  // d(alpha) of edge beg + lane
   for (int e0 = beg; e0 < end; e0 += 4) {
     const int ea = e0 + half, eb = e0 + 2 + half;
     const bool va = ea < end, vb = eb < end;
-    const float aa = va ? alpha[(long)ea * H + h] : 0.f, ab = vb ? alpha[(long)eb * H + h] : 0.f;
-    const float4 xa = (va && col4 >= 0) ? reinterpret_cast<const float4*>(value)[(long)ea * D4 + col4] : z4;
-    const float4 xb = (vb && col4 >= 0) ? reinterpret_cast<const float4*>(value)[(long)eb * D4 + col4] : z4;
+    const float4 xan = (ea + 4 < end && col4 >= 0) ? V[(long)(ea + 4) * D4 + col4] : z4;
+    const float4 xbn = (eb + 4 < end && col4 >= 0) ? V[(long)(eb + 4) * D4 + col4] : z4;
+    const int base = e0 - beg;  // wave-uniform, a multiple of 4
+    float aa = __shfl(al, (base + half) & 63), ab = __shfl(al, (base + 2 + half) & 63);
+    if (base >= 64) {
+      aa = va ? alpha[(long)ea * H + h] : 0.f;
+      ab = vb ? alpha[(long)eb * H + h] : 0.f;
+    }
+    if (!va) aa = 0.f;
+    if (!vb) ab = 0.f;
     const float keepa = keep_scale(seed, (unsigned long long)ea * H + h, drop_p);
     const float keepb = keep_scale(seed, (unsigned long long)eb * H + h, drop_p);
     float pa = xa.x * go.x + xa.y * go.y + xa.z * go.z + xa.w * go.w;
@@ -539,18 +625,26 @@ __global__ void attn_bwd_half_kernel(const float* __restrict__ alpha, const floa
     float contrib = aa * da + ab * db;           // this half's two edges
     contrib += __shfl_xor(contrib, 32);          // + the other half's
     s_acc += contrib;
-    if (gl == 0) {  // stash d(alpha); fixed up below
+    if (base < 64) {
+      // edges base .. base + 3 are (da, half 0), (da, half 1), (db, half 0), (db, half 1): lanes base .. base + 3 keep them
+      const float d0 = lane_value(da, 0), d1 = lane_value(da, 32), d2 = lane_value(db, 0), d3 = lane_value(db, 32);
+      if ((lane >> 2) == (base >> 2)) da_mine = (lane & 2) ? ((lane & 1) ? d3 : d2) : ((lane & 1) ? d1 : d0);
+    } else if (gl == 0) {  // rows longer than a wavefront: stash d(alpha) of the further edges; fixed up below
       if (va) d_logit[(long)ea * H + h] = da;
       if (vb) d_logit[(long)eb * H + h] = db;
     }
+    xa = xan, xb = xbn;
   }
-  // the stash above was written by lanes 0 / 32 of THIS wave and is re-read below by its other lanes: same wave, same CU,
-  // so both accesses go through this CU's write-through L1; the workgroup fence (s_waitcnt vmcnt(0)) retires the stores
-  // before the loads are issued.  No other wave touches these addresses.
-  __threadfence_block();
-  for (int e = beg + lane; e < end; e += 64) {
-    const float da = d_logit[(long)e * H + h];
-    d_logit[(long)e * H + h] = alpha[(long)e * H + h] * (da - s_acc);
+  if (lane < deg) d_logit[(long)(beg + lane) * H + h] = al * (da_mine - s_acc);
+  if (deg > 64) {
+    // the stash above was written by lanes 0 / 32 of THIS wave and is re-read below by its other lanes: same wave, same CU,
+    // so both accesses go through this CU's write-through L1; the workgroup fence (s_waitcnt vmcnt(0)) retires the stores
+    // before the loads are issued.  No other wave touches these addresses.
+    __threadfence_block();
+    for (int e = beg + 64 + lane; e < end; e += 64) {
+      const float da = d_logit[(long)e * H + h];
+      d_logit[(long)e * H + h] = alpha[(long)e * H + h] * (da - s_acc);
+    }
   }
 }
 
@@ -632,8 +726,12 @@ int eqf_gather_add_fwd(const float* a, const float* b, const int* src, const int
   if (D % 4 != 0) return EQF_E_UNSUPPORTED;
   if (E <= 0) return 0;
   const long total4 = (long)E * (D / 4);
-  hipLaunchKernelGGL(gather_add_kernel, dim3(eqf_cdiv(total4, 256)), dim3(256), 0, (hipStream_t)stream, a, b, src, dst,
-                     msg, total4, D / 4);
+  if (D / 4 >= GATHER_ROW_MIN_D4)  // a wave's 64 lanes would idle over narrower rows: those keep one float4 per thread
+    hipLaunchKernelGGL(gather_add_rows_kernel, dim3(eqf_cdiv(E, GATHER_WAVES * GATHER_ROWS)), dim3(64 * GATHER_WAVES), 0,
+                       (hipStream_t)stream, a, b, src, dst, msg, E, D / 4);
+  else
+    hipLaunchKernelGGL(gather_add_kernel, dim3(eqf_cdiv(total4, 256)), dim3(256), 0, (hipStream_t)stream, a, b, src, dst,
+                       msg, total4, D / 4);
   EQF_CHECK_LAUNCH();
   return 0;
 }
@@ -758,7 +856,7 @@ int eqf_alpha_fwd(const float* a, const float* alpha_dot, float* logit, int E, i
   if (!(Kh == 8 || Kh == 16 || Kh == 32 || Kh == 64)) return EQF_E_UNSUPPORTED;
   if (E <= 0) return 0;
   const long total = (long)E * H * Kh;
-  hipLaunchKernelGGL(alpha_fwd_kernel, dim3(eqf_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, a, alpha_dot,
+  hipLaunchKernelGGL(alpha_fwd_kernel, dim3(eqf_cdiv(total, 256 * ALPHA_U)), dim3(256), 0, (hipStream_t)stream, a, alpha_dot,
                      logit, total, H * Kh, Kh, c);
   EQF_CHECK_LAUNCH();
   return 0;

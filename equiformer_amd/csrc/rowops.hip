@@ -97,7 +97,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 // (Round 5 measured register-resident variants of the two kernels around this comment -- the row read once into 16 registers
 // per lane, per-segment sums formed from the registers: 23.5 us against 13.8 / 16.4 us at 2 304 rows.  The run-time loops
 // below are not the problem; the selects and index arithmetic of a segment-agnostic register layout cost more than the
-// re-reads from L1 they save.  Patch and A/B: profiles/r05/r05_k_*.)
+// re-reads from L1 they save.  Patch and A/B: profiles/r05/r05_k_*.  The per-segment register tile further down avoids both and
+// serves the rows that fit it; the two kernels around this comment serve every other layout: more than LN_REG_SEGS segments, or a
+// segment longer than 64 * LN_REG_K entries.)
 // Backward: dx = LN'(dy) (+ dres, the gradient arriving at the normalised sum from the residual branch); one wave per row.
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ dy, const float* __restrict__ dres,
@@ -137,6 +139,183 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       float v = rs * (g - sg - xh * sgx);
       if (rr) v += rr[T.off[s] + i];
       dr[T.off[s] + i] = v;
+    }
+  }
+}
+
+// Rows of at most LN_REG_SEGS segments of at most 64 * LN_REG_K entries each (QM9, MD17: 128 + 192 + 160).  The two kernels
+// above walk a row segment by segment, and inside a segment every pass waits for its own loads: 8-9 dependent round trips and
+// 6 reductions one after the other for 480 floats.  Here every load of the row -- the entries, their affine weights and biases,
+// the residual -- is requested before the first is used, into a PER-SEGMENT register tile: entry lane + 64 k of segment s is
+// xv[s][k], so the segment of a register is known at compile time (no select over segments per element, which is what made
+// the segment-agnostic tile of round 5 slow), the table entries are scalar operands, and the reductions of the segments are
+// independent chains that interleave.  A lane adds the same entries in the same order and the waves reduce with the same
+// butterfly as above, so y, rstd, mean0 and dx are bit-identical to the segment-by-segment kernels; absent segments
+// (s >= nseg) have len 0 in the zero-filled table and touch nothing.
+constexpr int LN_REG_SEGS = 4, LN_REG_K = 4;
+
+bool ln_fits_registers(const SegTab& T) {
+  if (T.nseg > LN_REG_SEGS) return false;
+  for (int s = 0; s < T.nseg; ++s)
+    if (T.len[s] > 64 * LN_REG_K) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void layernorm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ x2,
+                                                                float* __restrict__ xsum, const float* __restrict__ w,
+                                                                const float* __restrict__ b, float* __restrict__ y,
+                                                                float* __restrict__ rstd, float* __restrict__ mean0,
+                                                                int rows, SegTab T, float eps) {
+#pragma clang fp contract(off)  // the fused operations are written out: those of the kernel above, whatever the unrolling here
+  constexpr int S = LN_REG_SEGS, K = LN_REG_K;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* xr = x + (long)row * T.D;
+  const float* x2r = x2 ? x2 + (long)row * T.D : nullptr;
+  float* sr = x2 ? xsum + (long)row * T.D : nullptr;
+  float* yr = y + (long)row * T.D;
+  float xv[S][K], wv[S][K], bv[S][K];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int off = T.off[s], n = T.len[s], mul = max(T.mul[s], 1);
+    const float* ws = w + T.woff[s];
+    const int step = 64 % mul;
+    int u = lane % mul;  // (lane + 64 k) % mul, stepped without a division per entry
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = lane + 64 * k;
+      const bool ok = i < n;
+      xv[s][k] = ok ? xr[off + i] + (x2r ? x2r[off + i] : 0.f) : 0.f;
+      wv[s][k] = ok ? ws[u] : 0.f;
+      bv[s][k] = (ok && T.boff[s] >= 0) ? b[T.boff[s] + u] : 0.f;
+      u += step;
+      if (u >= mul) u -= mul;
+    }
+  }
+  float red[S], mean[S], rs[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (lane + 64 * k < T.len[s]) sum += xv[s][k];
+    red[s] = sum;
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) red[s] = wave_sum(red[s]);
+#pragma unroll
+  for (int s = 0; s < S; ++s) mean[s] = (s < T.nseg && T.l[s] == 0) ? red[s] / T.len[s] : 0.f;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    float sq = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (lane + 64 * k < T.len[s]) {
+        const float v = xv[s][k] - mean[s];
+        sq = fmaf(v, v, sq);
+      }
+    red[s] = sq;
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) red[s] = wave_sum(red[s]);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    if (s >= T.nseg) continue;
+    rs[s] = rsqrtf(red[s] / T.len[s] + eps);
+    if (lane == 0) {
+      rstd[(long)row * T.nseg + s] = rs[s];
+      if (T.l[s] == 0) mean0[(long)row * T.n0 + T.zidx[s]] = mean[s];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = lane + 64 * k;
+      if (i < T.len[s]) {
+        const float xe = xv[s][k];
+        if (sr) sr[T.off[s] + i] = xe;
+        float v = (xe - mean[s]) * rs[s] * wv[s][k];
+        if (T.boff[s] >= 0) v += bv[s][k];
+        yr[T.off[s] + i] = v;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void layernorm_bwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ dy, const float* __restrict__ dres,
+                                                                const float* __restrict__ rstd, float* __restrict__ dx,
+                                                                int rows, SegTab T) {
+#pragma clang fp contract(off)  // as in the forward: only the fused operations of layernorm_bwd_kernel, written out
+  constexpr int S = LN_REG_SEGS, K = LN_REG_K;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* xr = x + (long)row * T.D;
+  const float* gr = dy + (long)row * T.D;
+  const float* rr = dres ? dres + (long)row * T.D : nullptr;
+  float* dr = dx + (long)row * T.D;
+  float xv[S][K], gv[S][K], wv[S][K], rv[S][K], rs[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int off = T.off[s], n = T.len[s], mul = max(T.mul[s], 1);
+    const float* ws = w + T.woff[s];
+    const int step = 64 % mul;
+    int u = lane % mul;
+    rs[s] = s < T.nseg ? rstd[(long)row * T.nseg + s] : 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = lane + 64 * k;
+      const bool ok = i < n;
+      xv[s][k] = ok ? xr[off + i] : 0.f;
+      gv[s][k] = ok ? gr[off + i] : 0.f;
+      wv[s][k] = ok ? ws[u] : 0.f;
+      rv[s][k] = (ok && rr) ? rr[off + i] : 0.f;
+      u += step;
+      if (u >= mul) u -= mul;
+    }
+  }
+  float red[S], red2[S], mean[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (lane + 64 * k < T.len[s]) sum += xv[s][k];
+    red[s] = sum;
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) red[s] = wave_sum(red[s]);
+#pragma unroll
+  for (int s = 0; s < S; ++s) mean[s] = (s < T.nseg && T.l[s] == 0) ? red[s] / T.len[s] : 0.f;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    float sg = 0.f, sgx = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (lane + 64 * k < T.len[s]) {
+        const float g = gv[s][k] * wv[s][k];
+        const float xh = (xv[s][k] - mean[s]) * rs[s];
+        sg += g;
+        sgx += g * xh;
+      }
+    red[s] = sgx, red2[s] = sg;
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) red[s] = wave_sum(red[s]), red2[s] = wave_sum(red2[s]);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    if (s >= T.nseg) continue;
+    const float sgx = red[s] / T.len[s];
+    const float sg = (T.l[s] == 0) ? red2[s] / T.len[s] : 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = lane + 64 * k;
+      if (i < T.len[s]) {
+        const float xh = (xv[s][k] - mean[s]) * rs[s];
+        float v = rs[s] * fmaf(-sgx, xh, fmaf(gv[s][k], wv[s][k], -sg));  // g - sg - xh * sgx
+        if (rr) v += rv[s][k];
+        dr[T.off[s] + i] = v;
+      }
     }
   }
 }
@@ -410,6 +589,7 @@ __global__ __launch_bounds__(256) void silu_bwd_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------- LN(C<=64) + SiLU
+constexpr int LNSILU_ROWS = 4;  // rows per wave of the forward
 __global__ __launch_bounds__(256) void lnsilu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ y, int rows,
                                                          int C, float eps, int G) {
@@ -422,17 +602,26 @@ __global__ __launch_bounds__(256) void lnsilu_fwd_kernel(const float* __restrict
     beta += g_;
     y += g_;
   }
+  // A wave owns LNSILU_ROWS consecutive rows: their loads (and gamma, beta) are requested together and the two 64-lane
+  // reductions of each row are independent chains that interleave; one row per short-lived wave was load -> reduce ->
+  // reduce -> store with nothing to overlap.  Every row is still summed by the same lanes with the same butterfly.
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
-  if (row >= rows) return;
+  const int row0 = (blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6)) * LNSILU_ROWS;
+  if (row0 >= rows) return;
   const bool act = lane < C;
-  const float v = act ? x[(long)row * ld + lane] : 0.f;
-  const float mean = wave_sum(v) / C;
-  const float d = act ? v - mean : 0.f;
-  const float rs = rsqrtf(wave_sum(d * d) / C + eps);
-  if (act) {
-    const float z = d * rs * gamma[lane] + beta[lane];
-    y[(long)row * ld + lane] = z * sigmoidf_(z);
+  float v[LNSILU_ROWS];
+#pragma unroll
+  for (int r = 0; r < LNSILU_ROWS; ++r) v[r] = (act && row0 + r < rows) ? x[(long)(row0 + r) * ld + lane] : 0.f;
+  const float gm = act ? gamma[lane] : 0.f, bt = act ? beta[lane] : 0.f;
+#pragma unroll
+  for (int r = 0; r < LNSILU_ROWS; ++r) {
+    const float mean = wave_sum(v[r]) / C;
+    const float d = act ? v[r] - mean : 0.f;
+    const float rs = rsqrtf(wave_sum(d * d) / C + eps);
+    if (act && row0 + r < rows) {
+      const float z = d * rs * gm + bt;
+      y[(long)(row0 + r) * ld + lane] = z * sigmoidf_(z);
+    }
   }
 }
 
@@ -709,8 +898,9 @@ int eqf_add_layernorm_fwd(const float* x, const float* x2, float* xsum, const fl
   if ((x2 != nullptr) != (xsum != nullptr)) return EQF_E_BADARG;
   if (rows <= 0) return 0;
   const SegTab T = make_segtab(*irreps);
-  hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(eqf_cdiv(rows, WAVES_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, x, x2,
-                     xsum, weight, bias, y, rstd, mean0, rows, T, eps);
+  hipLaunchKernelGGL(ln_fits_registers(T) ? layernorm_fwd_reg_kernel : layernorm_fwd_kernel,
+                     dim3(eqf_cdiv(rows, WAVES_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, x, x2, xsum, weight, bias, y,
+                     rstd, mean0, rows, T, eps);
   EQF_CHECK_LAUNCH();
   return 0;
 }
@@ -727,8 +917,9 @@ int eqf_add_layernorm_bwd(const float* x, const float* weight, const float* dy, 
     return EQF_E_BADARG;
   if (rows <= 0) return 0;
   const SegTab T = make_segtab(*irreps);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(eqf_cdiv(rows, WAVES_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, x,
-                     weight, dy, dres, rstd, dx, rows, T);
+  hipLaunchKernelGGL(ln_fits_registers(T) ? layernorm_bwd_reg_kernel : layernorm_bwd_kernel,
+                     dim3(eqf_cdiv(rows, WAVES_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, x, weight, dy, dres, rstd, dx,
+                     rows, T);
   EQF_CHECK_LAUNCH();
   if (d_weight && d_bias) {
     hipLaunchKernelGGL(layernorm_wgrad_kernel, dim3(eqf_cdiv(T.D, 256), eqf_cdiv(rows, LN_WGRAD_ROWS)), dim3(256), 0,
@@ -830,7 +1021,7 @@ int eqf_lnsilu_group_fwd(const float* x, const float* gamma, const float* beta, 
   if (!x || !gamma || !beta || !y || C < 1 || groups < 1 || groups > 65535) return EQF_E_BADARG;
   if (C > 64) return EQF_E_UNSUPPORTED;
   if (rows <= 0) return 0;
-  hipLaunchKernelGGL(lnsilu_fwd_kernel, dim3(eqf_cdiv(rows, WAVES_PER_BLOCK), groups), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(lnsilu_fwd_kernel, dim3(eqf_cdiv(rows, WAVES_PER_BLOCK * LNSILU_ROWS), groups), dim3(256), 0, (hipStream_t)stream,
                      x, gamma, beta, y, rows, C, eps, groups);
   EQF_CHECK_LAUNCH();
   return 0;
